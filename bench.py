@@ -23,6 +23,12 @@ Workloads:
 Launch: python bench.py [--gpus N]  (N > 1 without torchrun: bench.py starts the N rank processes
 itself, as child processes, before anything touches a GPU)  or  torchrun --nproc-per-node N
 bench.py --gpus N.  --dry-run prints each rank's environment and exits before importing torch.
+
+A plain run sets up, warms up, times the steps and prints the result line (the roofline object is
+arithmetic over the timed steps' own statistics). --full adds what takes runs of its own: the
+untimed tie-count build, the CPU-baseline legs and the sampled parity against the oracle
+("cpu_baseline" and "parity" are null without it). --dump-outputs DIR writes the tables of the
+last timed step (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -79,6 +85,8 @@ VALU_LANE_CYCLES_T = 256 * 4 * 64 * 2.4e9 / 1e12
 VALU_ISSUE_T = 256 * 4 * 2.4e9 / 2 / 1e12
 FW_B = 64
 SHARD_ALIGN = 128  # row-shard / update-tile alignment (srt_device.h SRT_SHARD_ALIGN)
+DUMP_BYTES = 48 << 20  # --dump-outputs: lat.npy + rel.npy together (float64)
+DUMP_SEED = 20250101   # the row sample of --dump-outputs, the same in every run
 
 
 def cpu_threads() -> int:
@@ -175,8 +183,30 @@ class Ctx:
             dist.destroy_process_group()
 
 
+def dump_outputs(c: Ctx, lat, rel, rows: int, n: int, row0: int = 0):
+    """--dump-outputs DIR (rank 0, right after the timed steps, before anything builds again):
+    the tables the last timed step left in the caller's buffers, as DIR/lat.npy (latency quanta)
+    and DIR/rel.npy (reliabilities), both float64, [k, n]. Whole tables when they fit DUMP_BYTES,
+    else a fixed seeded sample of k of the `rows` rows this rank holds; DIR/rows.npy lists the
+    global row numbers (float64), row0 being the first local row's."""
+    d = c.args.dump_outputs
+    if not d or c.rank != 0:
+        return
+    k = max(1, min(rows, DUMP_BYTES // (2 * 8 * n)))
+    pick = np.arange(rows, dtype=np.int64)
+    if k < rows:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(rows, size=k, replace=False))
+    idx = torch.from_numpy(pick.astype(np.int64)).to(c.dev)
+    os.makedirs(d, exist_ok=True)
+    hl = lat.index_select(0, idx)[:, :n].contiguous().cpu().numpy()
+    np.save(os.path.join(d, "lat.npy"), hl.view(np.uint32).astype(np.float64))
+    np.save(os.path.join(d, "rel.npy"), rel.index_select(0, idx)[:, :n].contiguous().cpu().numpy())
+    np.save(os.path.join(d, "rows.npy"), (pick + row0).astype(np.float64))
+    log(c.rank, f"[bench] wrote {k} of {rows} rows of lat and rel to {d}")
+
+
 # ------------------------------------------------------------------------------------------
-# parity helpers (outside the timed region)
+# parity helpers (outside the timed region; --full)
 # ------------------------------------------------------------------------------------------
 def all_sum(c: Ctx, v: int) -> int:
     if c.world == 1:
@@ -289,6 +319,7 @@ def run_dense(c: Ctx, wl):
         _lib.check(rc, "build")
 
     elapsed, stats = c.timed(step)
+    dump_outputs(c, lat, rel, max(min(e, n) - b, 0), n, row0=b)
     c.last = stats[-1]
     c.ms_comm = [float(st.ms_comm) for st in stats]
     # dominant kernel: the FW update (phase 3) of every round, timed with HIP events on the
@@ -410,50 +441,8 @@ def run_dense(c: Ctx, wl):
                  "peak_basis": "256 CU x 4 SIMD x 64 lanes x 2.4 GHz / cycles_per_relax "
                                "(v_add_u32 2 cycles, packed/3-input ops 4 cycles per wave64)"},
     }
-    # untimed check build: the tied-pair count (srt_build_stats.tied_pairs), summed over ranks
-    chk = _lib.BuildStats()
-    chk.count_ties = 1
-    step(chk)
-    tied = all_sum(c, int(chk.tied_pairs))
-    # parity rows: rank 0's first / middle / last rows and the last rank's (gathered to rank 0)
-    sample = parity_rows(c, dense_range(c, n), n, k_per_rank=8)
-    glat, grel = gather_rows(c, sample, lambda rr: lat[rr], lambda rr: rel[rr], n, 1_000_000)
-    cpu = parity = None
-    if rank == 0 and not c.args.no_cpu_baseline:
-        import oracle  # cpu_baseline leg and the parity check only
-        if world == 1:
-            one = np.array([17 % n], np.int32)
-            _, _, _, t1 = oracle.complete_sample(n, wl["seed"], wl["lat_max"], wl["self_max"],
-                                                 wl["loss_max"], one, 1, metric=wl.get("metric", 0))
-            k = int(max(2, min(64, c.args.cpu_seconds / max(t1, 1e-3))))
-            srcs = np.unique(np.linspace(0, n - 1, k).astype(np.int32))
-            _, _, gen_s, sssp_s = oracle.complete_sample(n, wl["seed"], wl["lat_max"],
-                                                         wl["self_max"], wl["loss_max"], srcs, 1,
-                                                         metric=wl.get("metric", 0))
-            cpu = {"value": round(len(srcs) * n / sssp_s, 1), "unit": "node-pairs/s", "cores": 1,
-                   "kind": "port",
-                   "sample": f"{len(srcs)} of {n} sources, dense O(n^2) Dijkstra per source "
-                             f"(oracle/oracle.c orc_complete_sample), {sssp_s:.1f} s, 1 thread "
-                             f"(the reference serializes Dijkstra on graphLock, topology.c:130-148); "
-                             f"matrix generation ({gen_s:.1f} s) excluded"}
-            # all-cores leg (SURVEY §8d ii): the same per-source Dijkstra sharded over host threads
-            nt = cpu_threads()
-            kk = int(max(nt, min(32 * nt, nt * c.args.cpu_seconds / 2 / max(t1, 1e-3))))
-            msrcs = np.unique(np.linspace(0, n - 1, kk).astype(np.int32))
-            _, _, _, mt_s = oracle.complete_sample(n, wl["seed"], wl["lat_max"], wl["self_max"],
-                                                   wl["loss_max"], msrcs, nt,
-                                                   metric=wl.get("metric", 0))
-            cpu["all_cores"] = {"value": round(len(msrcs) * n / mt_s, 1), "cores": nt,
-                                "sample": f"{len(msrcs)} of {n} sources over {nt} threads, "
-                                          f"{mt_s:.1f} s (no graphLock: the reference cannot do "
-                                          f"this)"}
-        # full-size parity of the last build's rows against the oracle
-        clat, crel, _, _ = oracle.complete_sample(n, wl["seed"], wl["lat_max"], wl["self_max"],
-                                                  wl["loss_max"], sample, cpu_threads(),
-                                                  metric=wl.get("metric", 0))
-        parity = compare_rows(sample, n, glat, grel, clat, crel)
-    if parity is not None:
-        parity.update({"tied_pairs": tied, "tied_frac": tied / float(n * (n - 1))})
+    # --full: the tied-pair count (an untimed check build), the CPU baseline and the parity rows
+    cpu, parity = dense_cpu_and_parity(c, wl, step, lat, rel)
     s0 = stats[-1]
     # pivots per round (one C-tile residency): 256 (enc 7, 9), 128 (enc 6, 8), else the 64-pivot
     # diagonal block FW_B
@@ -469,7 +458,10 @@ def run_dense(c: Ctx, wl):
 
 
 def dense_cpu_and_parity(c: Ctx, wl, step, lat, rel):
-    """untimed: the tied-pair count (check build), the CPU baseline legs and the sampled parity"""
+    """--full, untimed: the tied-pair count (check build), the CPU baseline legs and the sampled
+    parity; (None, None) in a plain run"""
+    if not c.args.full:
+        return None, None
     n, world, rank = wl["n"], c.world, c.rank
     chk = _lib.BuildStats()
     chk.count_ties = 1
@@ -663,6 +655,7 @@ def run_sparse(c: Ctx, wl):
             comm_ms.append(ea.elapsed_time(eb))
 
     elapsed, stats = c.timed(step)
+    dump_outputs(c, lat, rel, n, n)  # after the all-gather every rank holds every row
     c.last = stats[-1]
     c.ms_comm = list(comm_ms) if comm_ms else [0.0] * len(stats)
     arcs = sg.arcs
@@ -744,6 +737,27 @@ def run_sparse(c: Ctx, wl):
         roofline["valu"] = valu
     if others:
         roofline["kernels"] = others
+    cpu, parity = sparse_cpu_and_parity(c, g, sg, step, lat, rel, per)
+    sg.free()
+    s0st = stats[-1]
+    config = {"workload": wl["desc"], "n": n, "edges": int(g.m), "arcs": int(arcs),
+              "parallelism": f"source-shard x{world}" + (" + RCCL allgather" if world > 1 else ""),
+              "sources_per_rank": nsrc,
+              "sources_recomputed_after_bucket_overflow": int(s0st.ess_arcs),
+              "kernel_form": int(s0st.fw_block),
+              # srt_build_stats.fw_block bit 64: the independent set's rows derived from their
+              # neighbours' (derive.hip) instead of run by the kernel
+              "derived_rows": bool(int(s0st.fw_block) & 64),
+              "ms_sssp": round(s0st.ms_fw, 3)}
+    return elapsed, "u32", "strong", config, roofline, cpu, parity
+
+
+def sparse_cpu_and_parity(c: Ctx, g, sg, step, lat, rel, per):
+    """--full, untimed: the tied-pair count (check build), the CPU baseline legs and the sampled
+    parity of a sparse build; (None, None) in a plain run"""
+    if not c.args.full:
+        return None, None
+    n, world, rank = g.n, c.world, c.rank
     # untimed check build: the tied-pair count over this rank's rows, summed over ranks
     chk = _lib.BuildStats()
     chk.count_ties = 1
@@ -794,18 +808,7 @@ def run_sparse(c: Ctx, wl):
         parity = compare_rows(sample, n, glat, rel_rows, ex["lat_int"], ex["rel"])
     if parity is not None:
         parity.update({"tied_pairs": tied, "tied_frac": tied / float(n * (n - 1))})
-    sg.free()
-    s0st = stats[-1]
-    config = {"workload": wl["desc"], "n": n, "edges": int(g.m), "arcs": int(arcs),
-              "parallelism": f"source-shard x{world}" + (" + RCCL allgather" if world > 1 else ""),
-              "sources_per_rank": nsrc,
-              "sources_recomputed_after_bucket_overflow": int(s0st.ess_arcs),
-              "kernel_form": int(s0st.fw_block),
-              # srt_build_stats.fw_block bit 64: the independent set's rows derived from their
-              # neighbours' (derive.hip) instead of run by the kernel
-              "derived_rows": bool(int(s0st.fw_block) & 64),
-              "ms_sssp": round(s0st.ms_fw, 3)}
-    return elapsed, "u32", "strong", config, roofline, cpu, parity
+    return cpu, parity
 
 
 def free_port() -> int:
@@ -861,12 +864,21 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="c4", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the untimed checks: the tie-count build, "
+                         "the CPU-baseline legs and the sampled parity against the oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's tables to DIR/lat.npy, DIR/rel.npy (float64; "
+                         "a fixed seeded row sample when they are large) and DIR/rows.npy")
     ap.add_argument("--cpu-seconds", type=float, default=15.0,
-                    help="budget of the CPU-baseline sample (rank 0, N=1 only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="with --full: budget of the CPU-baseline sample (rank 0, N=1 only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: keep the tie-count build, skip the oracle legs")
     ap.add_argument("--dry-run", action="store_true",
                     help="print this rank's launch environment and exit before importing torch")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch(args.gpus))
     if args.dry_run:  # one write per line: the ranks share the launcher's stdout

@@ -9,7 +9,7 @@
  * candidates of the next pass) once some lane of it is below the bucket bound T; otherwise it waits
  * in the pending set until T passes it (delta-stepping over the lane minimum).
  * jacobi = 1 computes each pass from the previous pass's states (the GPU's worst case), 0 in place.
- * Built as a shared library: gcc -O2 -shared -fPIC tools/msssp_sim.c -o /tmp/libmsssp_sim.so
+ * Built as a shared library: gcc -O2 -shared -fPIC tools/msssp_sim.c -o libmsssp_sim.so
  */
 #include <stdint.h>
 #include <stdlib.h>

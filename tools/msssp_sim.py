@@ -10,13 +10,13 @@ import ctypes
 import os
 import subprocess
 import sys
+import tempfile
 
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 from shadow_amd import graphs  # noqa: E402
 
-SO = "/tmp/libmsssp_sim.so"
 
 
 class Counts(ctypes.Structure):
@@ -26,9 +26,14 @@ class Counts(ctypes.Structure):
 
 
 def load():
-    src = os.path.join(os.path.dirname(__file__), "msssp_sim.c")
-    subprocess.check_call(["gcc", "-O2", "-shared", "-fPIC", src, "-o", SO])
-    return ctypes.CDLL(SO)
+    """Build msssp_sim.c into a directory of this call's own (a fixed path under the shared
+    temporary directory could belong to another user) and load it; the loaded library outlives
+    the directory."""
+    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "msssp_sim.c")
+    with tempfile.TemporaryDirectory(prefix="msssp_sim_") as d:
+        so = os.path.join(d, "libmsssp_sim.so")
+        subprocess.check_call(["gcc", "-O2", "-shared", "-fPIC", src, "-o", so])
+        return ctypes.CDLL(so)
 
 
 def csr(g):

@@ -54,7 +54,7 @@ run_step() {
         local st=${b:-5} sfx=""
         [ -n "$c" ] && sfx="_$(echo $c | tr '+=' '__')"
         env $(envs "$c") timeout -k 10 600 python -u bench.py --workload $a --steps $st \
-            --warmup 1 > $O/bench_$a$sfx.json 2> $O/bench_$a$sfx.err ;;
+            --warmup 1 --full >$O/bench_$a$sfx.json 2> $O/bench_$a$sfx.err ;;
     prof)
         local sfx=""
         [ -n "$b" ] && sfx="_$(echo $b | tr '+=' '__')"
