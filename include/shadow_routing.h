@@ -105,7 +105,7 @@ typedef struct srt_build_stats {
                           * gathered over all levels, counted on the device -- a unit stops early
                           * once its sources are settled), 0 where the bench models them itself */
     double ms_pred;      /* level builds (time_kernels = 1): HIP-event time of the predecessor pass
-                          * (lvl_pred_kernel) */
+                          * (lvl_pred_kernel, with lvl_pred_near_kernel's pre-pass when taken) */
     double ms_rel;       /* ... and of the path-order reliability pass (rel_tree_kernel and the
                           * sweeps of the rows it hands over) */
     int32_t n_derived;   /* sparse full-table builds with derived rows (fw_block bit 64): the rows
@@ -120,6 +120,11 @@ typedef struct srt_build_stats {
     double ms_upload;    /* ... the dense matrices filled from it and moved to the device (pinned
                           * two-slot staging; the slowest rank of a sharded build) */
     double ms_download;  /* ... the tables moved into the caller's buffers (same staging) */
+    int32_t pred_near;   /* dense level builds: the bucket capacity of the predecessor pre-pass
+                          * (lvl_pred_near_kernel: the Delta_1 arc groups resolved from the in-arc
+                          * runs), 0 = not taken */
+    int32_t pred_near_over; /* ... its buckets that passed the capacity (their units walk the
+                             * groups as without the pre-pass) */
 } srt_build_stats;
 
 /* Build the full tables for an edge list on one GPU; outputs are host buffers of n*n entries.

@@ -74,6 +74,8 @@ class BuildStats(ctypes.Structure):
         ("ms_canon", ctypes.c_double),
         ("ms_upload", ctypes.c_double),
         ("ms_download", ctypes.c_double),
+        ("pred_near", ctypes.c_int32),
+        ("pred_near_over", ctypes.c_int32),
     ]
 
 

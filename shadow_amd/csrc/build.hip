@@ -2005,6 +2005,7 @@ static int build_multi(const srt_canon* c, const srt_build_opts* opts, int algo,
             *stats = jobs[0].st;
             for (int i = 1; i < R; i++) {
                 stats->tied_pairs += jobs[i].st.tied_pairs;
+                stats->pred_near_over += jobs[i].st.pred_near_over;
                 if (jobs[i].st.ms_upload > stats->ms_upload) stats->ms_upload = jobs[i].st.ms_upload;
                 if (jobs[i].st.ms_download > stats->ms_download)
                     stats->ms_download = jobs[i].st.ms_download;

@@ -1946,7 +1946,9 @@ __global__ __launch_bounds__(256) void dense_diag_kernel(int n, int ld, int row0
 /* ------------------------------------------------------------------------------------------ */
 typedef struct {
     size_t n_cap, arc_cap, tarc_cap;
-    int32_t *cnt, *ptr, *tptr, *cursor, *col, *tcol, *depth;
+    int32_t *cnt, *ptr, *tptr, *cursor, *col, *tcol;
+    int32_t* depth; /* [0] the deepest tree of the reliability pass, [1] the level predecessor
+                     * pre-pass's overflowed buckets (read back together) */
     unsigned long long* ties; /* tied-pair count of the predecessor pass */
     uint32_t *aw, *tw;
     double *ar, *tr;
@@ -1968,6 +1970,7 @@ typedef struct {
     int diag_done; /* the level post pass applied the diagonal rule itself */
     int pred16;    /* dt holds int16 predecessor rows (level post pass, n <= 32768; 2: packed
                     * predecessor | reliability index words) */
+    int pn_cap;    /* the level post pass took lvl_pred_near_kernel with this bucket capacity */
 } dense_ws;
 
 static dense_ws g_ws[SRT_STATE_SLOTS];
@@ -1998,7 +2001,7 @@ static int ws_get(dense_ws** out, int n) {
         SRT_HIPCHK(hipMalloc(&ws->ptr, c * sizeof(int32_t)));
         SRT_HIPCHK(hipMalloc(&ws->tptr, c * sizeof(int32_t)));
         SRT_HIPCHK(hipMalloc(&ws->cursor, c * sizeof(int32_t)));
-        SRT_HIPCHK(hipMalloc(&ws->depth, sizeof(int32_t)));
+        SRT_HIPCHK(hipMalloc(&ws->depth, 2 * sizeof(int32_t)));
         SRT_HIPCHK(hipMalloc(&ws->ties, sizeof(unsigned long long)));
         ws->n_cap = c;
     }
@@ -2229,8 +2232,8 @@ static int dense_post_levels(int32_t n, int32_t ld, int32_t row0, int32_t nrows,
         SRT_HIPCHK(hipMemsetAsync(rel + (size_t)lrows * ld, 0, (size_t)(nrows - lrows) * ld * sizeof(double), st));
     }
     if (lrows > 0 && srt_levels_pkw_ready()) {
-        /* source-major packed words (lvl_pkw_kernel) + rel_pk_kernel, which writes the u32 rows
-         * too: 4 B per pair written and read between them, no transposes, no u8 rows */
+        /* target-major packed words with the level (lvl_pred_kernel), one u32 transpose, then
+         * rel_pk_kernel, which writes the u32 rows too: no u8 rows, no f64 slab */
         const size_t slab = (size_t)ld * nrows;
         size_t c1 = ws->dt_cap;
         if ((rc = ws_grow((void**)&ws->dt, &c1, slab, sizeof(uint32_t)))) return rc;
@@ -2249,8 +2252,9 @@ static int dense_post_levels(int32_t n, int32_t ld, int32_t row0, int32_t nrows,
             size_t c2 = ws->predt_cap;
             if ((rc = ws_grow((void**)&ws->predt, &c2, slab, sizeof(int32_t)))) return rc;
             ws->predt_cap = c2;
+            SRT_HIPCHK(hipMemsetAsync(ws->depth + 1, 0, sizeof(int32_t), st));
             if ((rc = srt_levels_pred(ws->predt, 2, nullptr, (size_t)nrows, ties ? ws->ties : NULL,
-                                      st)))
+                                      ws->depth + 1, &ws->pn_cap, st)))
                 return rc;
         }
         if (kt) SRT_HIPCHK(hipEventRecord(ws->kev[1], st));
@@ -2290,7 +2294,9 @@ static int dense_post_levels(int32_t n, int32_t ld, int32_t row0, int32_t nrows,
         const double* rtab = n <= 32768 ? srt_levels_rtab(&ntab) : nullptr;
         const int p16 = rtab ? 2 : n <= 32768;
         if (stats) stats->rel_table = rtab ? ntab : 0;
-        if ((rc = srt_levels_pred(ws->predt, p16, ws->rt, (size_t)nrows, ties ? ws->ties : NULL, st)))
+        SRT_HIPCHK(hipMemsetAsync(ws->depth + 1, 0, sizeof(int32_t), st));
+        if ((rc = srt_levels_pred(ws->predt, p16, ws->rt, (size_t)nrows, ties ? ws->ties : NULL,
+                                  ws->depth + 1, &ws->pn_cap, st)))
             return rc;
         if (kt) SRT_HIPCHK(hipEventRecord(ws->kev[1], st));
         int32_t* pred = reinterpret_cast<int32_t*>(ws->dt);
@@ -2353,14 +2359,18 @@ static int dense_finish_rows(int32_t n, int32_t ld, int32_t row0, int32_t nrows,
         dense_ws* ws;
         int rc = ws_get(&ws, n);
         if (rc) return rc;
-        int32_t depth = 0;
+        int32_t depth[2] = {0, 0};
         unsigned long long nt = 0;
-        SRT_HIPCHK(hipMemcpyAsync(&depth, ws->depth, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        SRT_HIPCHK(hipMemcpyAsync(depth, ws->depth, (ws->pn_cap ? 2 : 1) * sizeof(int32_t),
+                                  hipMemcpyDeviceToHost, st));
         if (stats->count_ties)
             SRT_HIPCHK(hipMemcpyAsync(&nt, ws->ties, sizeof(nt), hipMemcpyDeviceToHost, st));
         SRT_HIPCHK(hipStreamSynchronize(st));
-        stats->max_depth = depth;
+        stats->max_depth = depth[0];
         stats->tied_pairs = (int64_t)nt;
+        stats->pred_near = ws->pn_cap;
+        stats->pred_near_over = depth[1];
+        ws->pn_cap = 0;
         dense_collect_total(n, stats);
         if (ws->kev_on) {
             float a = 0, b = 0;

@@ -1310,6 +1310,108 @@ __global__ void lvl_segs_kernel(int ld, const int32_t* __restrict__ off, int32_t
     if (j <= ld) seg[j] = off[(size_t)j * LVL_STRIDE];
 }
 
+/* The predecessor pass's Delta_1 groups from the in-arc runs, before lvl_pred_kernel (the form of
+ * lvl_near_kernel: one wave per target t, every chunk at once). At level d the walk's group
+ * w = d - 1 reads Delta_1[u] for each in-arc (u, d - 1) -- u's weight-1 run of in-arcs, ~97% zero
+ * words as a plane row on C4 -- and cannot stop early, so it is most of a unit's gathers. Here the
+ * wave keeps Delta_d[t] in LDS, clears the sources of t's own weight-d arcs (the direct arc wins),
+ * then takes the arcs (u, d - 1) in arc order and each run's sources s one per lane: a
+ * test-and-clear of s's bit (the LDS unit applies a wave's atomics in issue order, and a run's
+ * sources are distinct) leaves the bit to the first arc that is tight for (s, t) -- the walk's
+ * canonical arc, largest weight after the direct one and smallest u inside it. Each winner goes
+ * to the bucket of (t, chunk of s) as source-in-chunk | (arc - off[t][0]) << 11, the u16 arc
+ * index the walk keeps in sidx; the order inside a bucket is free (a source appears once). A
+ * bucket holds cap entries: an append past cap only leaves the unit's count above cap, and
+ * lvl_pred_unit then walks that unit's Delta_1 groups itself. LDS per wave: nw row words and
+ * nchunk counters. */
+__global__ __launch_bounds__(256) void lvl_pred_near_kernel(int n, int nw, int nchunk, int src0, int nsrc,
+                                                            int nlev, int cap,
+                                                            const int32_t* __restrict__ off,
+                                                            const uint32_t* __restrict__ arcs,
+                                                            const uint32_t* __restrict__ lev,
+                                                            uint32_t* __restrict__ bkt,
+                                                            uint32_t* __restrict__ bcnt,
+                                                            int32_t* __restrict__ nover) {
+    extern __shared__ uint32_t pn_lds[]; /* per wave: nw row words, then nchunk counters */
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int t = blockIdx.x * 4 + wv;
+    if (t >= n) return; /* (no workgroup barrier below: a wave works alone) */
+    uint32_t* row = pn_lds + (size_t)wv * (nw + nchunk);
+    uint32_t* cnt = row + nw;
+    const size_t plane = (size_t)n * nw;
+    const int32_t* ot = off + (size_t)t * LVL_STRIDE;
+    const int a_t = ot[0];
+    uint32_t* tb = bkt + (size_t)t * nchunk * cap;
+    for (int i = lane; i < nchunk; i += 64) cnt[i] = 0u;
+    /* s (local index ks) found through arc i: its bit test-and-cleared, the winner appended */
+    auto claim = [&](int ks, int i) {
+        const uint32_t bit = 1u << (ks & 31);
+        if (atomicAnd(&row[ks >> 5], ~bit) & bit) {
+            const int c = ks >> 11;
+            const uint32_t pos = atomicAdd(&cnt[c], 1u);
+            if (pos < (uint32_t)cap) tb[(size_t)c * cap + pos] = (uint32_t)(ks & 2047) | (uint32_t)(i - a_t) << 11;
+        }
+    };
+    for (int d = 2; d <= nlev; ++d) {
+        const uint32_t* prow = lev + (size_t)(d - 1) * plane + (size_t)t * nw;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        uint32_t any = 0;
+        for (int i = lane; i < nw; i += 64) any |= (row[i] = prow[i]);
+        if (!__any(any != 0u)) continue; /* no source at this level */
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        for (int i = ot[d] + lane; i < ot[d + 1]; i += 64) { /* the direct arcs keep their sources */
+            const int ks = (int)(arcs[i] & 0xFFFFu) - src0;
+            if (ks >= 0 && ks < nsrc) atomicAnd(&row[ks >> 5], ~(1u << (ks & 31)));
+        }
+        /* the runs' bounds of 64 arcs in one vector load per lane, four runs' first 64 entries in
+         * flight together (lvl_near_kernel's schedule), their updates strictly in arc order */
+        const int a1 = ot[d];
+        for (int c0 = ot[d - 1]; c0 < a1; c0 += 64) {
+            int ub0 = 0, ub1 = 0;
+            if (c0 + lane < a1) {
+                const int u = (int)(arcs[c0 + lane] & 0xFFFFu);
+                ub0 = off[(size_t)u * LVL_STRIDE + 1];
+                ub1 = off[(size_t)u * LVL_STRIDE + 2];
+            }
+            const int na = min(64, a1 - c0);
+            for (int k = 0; k < na; k += 4) {
+                uint32_t e[4];
+                int b0[4], b1[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    b0[q] = k + q < na ? __builtin_amdgcn_readlane(ub0, k + q) : 0;
+                    b1[q] = k + q < na ? __builtin_amdgcn_readlane(ub1, k + q) : 0;
+                    e[q] = b0[q] + lane < b1[q] ? arcs[b0[q] + lane] : 0xFFFFFFFFu;
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int ks = (int)(e[q] & 0xFFFFu) - src0;
+                    if (e[q] != 0xFFFFFFFFu && ks >= 0 && ks < nsrc) claim(ks, c0 + k + q);
+                    for (int i = b0[q] + 64 + lane; i < b1[q]; i += 64) { /* (runs past 64) */
+                        const int kt = (int)(arcs[i] & 0xFFFFu) - src0;
+                        if (kt >= 0 && kt < nsrc) claim(kt, c0 + k + q);
+                    }
+                }
+            }
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    int over = 0;
+    for (int i = lane; i < nchunk; i += 64) {
+        const uint32_t k = cnt[i];
+        bcnt[(size_t)t * nchunk + i] = k;
+        over += k > (uint32_t)cap;
+    }
+    for (int m = 32; m > 0; m >>= 1) over += __shfl_xor(over, m);
+    if (lane == 0 && over) atomicAdd(nover, over);
+}
+
 /* PT = uint32_t: the packed form -- one word per pair, (u16) predecessor | reliability index << 16
  * (the arc's reliability is rtab[index], lvl_rtab_*), written into predT; rT and ar unused */
 /* Canonical predecessors from the levels (the rule of every build kernel: among the tight in-arcs
@@ -1323,7 +1425,8 @@ __global__ void lvl_segs_kernel(int ld, const int32_t* __restrict__ off, int32_t
  * as soon as every source of the wave has its arc. Outputs, target-major as pred_cols*_kernel's
  * (stride ldp): predT[t][sl] = u (-1 on the diagonal), rT[t][sl] = r(u, t). */
 template <typename PT>
-static __device__ __forceinline__ void lvl_pred_unit(unsigned g, uint16_t (*sidx)[64 * 40], int n,
+static __device__ __forceinline__ void lvl_pred_unit(unsigned g, uint16_t (*sidx)[64 * 40],
+                                                     int n,
                                                      int nw, int nchunk, int src0, int nsrc, int nlev,
                                                        const int32_t* __restrict__ off,
                                                        const uint32_t* __restrict__ arcs,
@@ -1333,7 +1436,9 @@ static __device__ __forceinline__ void lvl_pred_unit(unsigned g, uint16_t (*sidx
                                                        const uint32_t* __restrict__ lev,
                                                        PT* __restrict__ predT,
                                                        double* __restrict__ rT, size_t ldp,
-                                                       unsigned long long* __restrict__ ties) {
+                                                       unsigned long long* __restrict__ ties,
+                                                       const uint32_t* __restrict__ bkt,
+                                                       const uint32_t* __restrict__ bcnt, int cap) {
     constexpr bool PK = std::is_same_v<PT, uint32_t>;
     const int tgrp = (n + 3) >> 2;
     const int c = (int)(g / (unsigned)tgrp);
@@ -1351,6 +1456,33 @@ static __device__ __forceinline__ void lvl_pred_unit(unsigned g, uint16_t (*sidx
     const int a_t = ot[0];
     const uint32_t lane4 = (uint32_t)(valid ? word : 0) * 4u;
     unsigned tied = 0;
+    /* lvl_pred_near_kernel's bucket of this unit: the pairs whose arc is in a Delta_1 group
+     * (w = d - 1), each into its source's sidx slot and its bit into the claimed word of the
+     * lane that owns the source -- u16 slots 32-33 of the lane's 40 in sidx, which the read-back
+     * leaves spare: no LDS added, and the word is re-read per level through the lane's sidx
+     * address (no register held across the walk). A bucket that
+     * overflowed is ignored and the groups are walked as without the pre-pass. */
+    bool pn = false;
+    if (bkt) {
+        const size_t un = (size_t)t * nchunk + c;
+        const int k = __builtin_amdgcn_readfirstlane((int)bcnt[un]);
+        pn = k <= cap;
+        if (pn) {
+            *reinterpret_cast<uint32_t*>(my + 32) = 0u;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            const uint32_t* ub = bkt + un * cap;
+            for (int i = lane; i < k; i += 64) {
+                const uint32_t e = ub[i], sl = e & 2047u;
+                sidx[wv][(sl >> 5) * 40 + (sl & 31u)] = (uint16_t)(e >> 11);
+                atomicOr(reinterpret_cast<uint32_t*>(&sidx[wv][(sl >> 5) * 40 + 32]), 1u << (sl & 31u));
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
+    }
     /* one arc's candidates: x = its tight sources among the pending ones */
     auto take = [&](uint32_t x, uint32_t& H, uint32_t& T, int i) {
         uint32_t nb = x & ~H;
@@ -1361,8 +1493,6 @@ static __device__ __forceinline__ void lvl_pred_unit(unsigned g, uint16_t (*sidx
             nb &= nb - 1u;
         }
     };
-    /* PK: the level of each of the lane's 32 sources as five bit planes (level <= 31), so the
-     * packed word carries it (pred | rix << 16 | level << 27) for rel_pk_kernel */
     uint32_t lvb[5] = {0u, 0u, 0u, 0u, 0u};
     for (int d = 1; d <= nlev; ++d) {
         uint32_t pend = valid ? lev[(size_t)(d - 1) * plane + (size_t)t * nw + word] : 0u;
@@ -1371,8 +1501,11 @@ static __device__ __forceinline__ void lvl_pred_unit(unsigned g, uint16_t (*sidx
             for (int k = 0; k < 5; ++k)
                 if ((d >> k) & 1) lvb[k] |= pend;
         }
+        if (pn) pend &= ~*reinterpret_cast<const uint32_t*>(my + 32);
         if (!__any(pend != 0u)) continue;
+        const int skip = pn ? d - 1 : 0; /* (w >= 1) */
         for (int w = d; w >= 1; --w) {
+            if (w == skip) continue; /* lvl_pred_near_kernel took this group's pairs */
             const int g0 = ot[w], g1 = ot[w + 1];
             if (g0 == g1) continue;
             uint32_t H = 0, T = 0;
@@ -1511,8 +1644,13 @@ template <typename PT>
 /* The units walked chunk-major by all eight XCDs together (block u * 8 + XCD): the planes'
  * gathered slices are one source chunk's at a time for the whole GPU (8 MB per plane, in the
  * MALL), where XCD-private runs of chunks had 16 chunks' slices in flight (~384 MB on C4): 8.16
- * against 8.40 ms on C4. */
-__global__ __launch_bounds__(256) void lvl_pred_kernel(int n, int nw, int nchunk, int src0, int nsrc,
+ * against 8.40 ms on C4.
+ * Seven waves per SIMD are asked for: with the bucket code the register allocator, left alone,
+ * settles at 77 VGPRs (six waves: 5.66 against 5.14 ms on C4 without the pre-pass); at 72 it
+ * spills two registers of the packed form (12 B of scratch per lane) and the walk keeps its
+ * rate (5.20). The level bit planes stay in registers: reading the plane words a second time in
+ * the output stage instead (70 VGPRs, no spill) measured 7.9 ms. */
+__global__ __launch_bounds__(256, 7) void lvl_pred_kernel(int n, int nw, int nchunk, int src0, int nsrc,
                                                        int nlev, unsigned nblk,
                                                        const int32_t* __restrict__ off,
                                                        const uint32_t* __restrict__ arcs,
@@ -1522,14 +1660,16 @@ __global__ __launch_bounds__(256) void lvl_pred_kernel(int n, int nw, int nchunk
                                                        const uint32_t* __restrict__ lev,
                                                        PT* __restrict__ predT,
                                                        double* __restrict__ rT, size_t ldp,
-                                                       unsigned long long* __restrict__ ties) {
+                                                       unsigned long long* __restrict__ ties,
+                                                       const uint32_t* __restrict__ bkt,
+                                                       const uint32_t* __restrict__ bcnt, int cap) {
     /* per wave and lane: the winning arc of each of its 32 sources (index into t's arcs), 40 u16
      * per lane so the read-back is four 16-B loads */
     __shared__ __attribute__((aligned(16))) uint16_t sidx[4][64 * 40];
     const unsigned x = blockIdx.x & 7u, per = nblk >> 3, L = gridDim.x >> 3;
     for (unsigned u = blockIdx.x >> 3; u < per; u += L)
         lvl_pred_unit<PT>(u * 8u + x, sidx, n, nw, nchunk, src0, nsrc, nlev, off, arcs, aoff, ar,
-                          rix, lev, predT, rT, ldp, ties);
+                          rix, lev, predT, rT, ldp, ties, bkt, bcnt, cap);
 }
 
 __global__ void lvl_sum_kernel(const unsigned long long* __restrict__ v, int k,
@@ -1571,6 +1711,34 @@ static int lvl_budget(const unsigned long long* hist, double ntgt, double nw, do
     return L;
 }
 
+/* Bucket capacity of lvl_pred_near_kernel from the weight histogram: the expected entries of a
+ * unit (one target, up to 2,048 sources) with headroom, as a power of two. A pair (s, t) enters a
+ * bucket at level d when some in-arc (u, d - 1) of t has s in u's weight-1 run -- probability
+ * c_d = a[d-1] * a[1] / n with a[w] = hist[w] / n arcs of weight w into a vertex -- and no walk
+ * shorter than d joins the pair. The walks of total weight k between a pair are taken as Poisson
+ * with mean N[k] = hist[k] / n^2 + sum_w a[w] * N[k-w] (random arcs), so the pair is still open at
+ * level d with probability exp(-sum_{k<d} N[k]). On C4 (a ~ 33, n = 32,768) this gives 3.3% at
+ * levels 2 and 3 and 1.0% at level 4, 155 entries per unit; six standard deviations of headroom
+ * make it 256. A unit past its capacity only falls back to the walk, so the model need not be
+ * safe, and a dense Delta_1 gives a capacity past 1,024, which turns the pre-pass off. */
+static int lvl_pn_cap(const unsigned long long* hist, int n, int nsrc, int D) {
+    const double dn = (double)n;
+    double N[LVL_WMAX + 2], below = 0, mean = 0;
+    D = min(D, LVL_WMAX);
+    for (int d = 1; d <= D; ++d) {
+        double x = (double)hist[d] / (dn * dn);
+        for (int w = 1; w < d; ++w) x += (double)hist[w] / dn * N[d - w];
+        N[d] = x;
+        if (d >= 2) mean += fmin(1.0, (double)hist[d - 1] / dn * (double)hist[1] / dn / dn) * exp(-below);
+        below += x;
+    }
+    mean *= (double)min(2048, nsrc);
+    const double need = mean + 6.0 * sqrt(mean);
+    int cap = 16;
+    while (cap < 2048 && (double)cap < need) cap <<= 1;
+    return (double)cap < need ? 4096 : cap; /* (4096: more than a bucket can ever hold) */
+}
+
 /* persistent grid of a 256-thread unit kernel: its resident workgroups per CU x the CUs, a multiple
  * of 8 (one share per XCD), at most the unit blocks */
 static unsigned lvl_grid(const void* fn, unsigned nblk, int reserve_cus = 0) {
@@ -1603,6 +1771,7 @@ typedef struct {
     uint8_t* l8; /* u8 distance rows (nrows x ld) for the reliability pass */
     int pkw;     /* the post pass is the packed words with levels + rel_pk (no lat / l8 rows) */
     int total;   /* in-arcs held (w <= lmax) */
+    int pn_cap;  /* lvl_pred_near_kernel: the bucket capacity the weight histogram asks for */
     unsigned long long* dkey; /* the diagonal rule's key per local row (undirected rows form) */
     const double* r_rows;
     void* p[40]; /* every allocation of the build (LVL_ALLOC), freed together */
@@ -2532,6 +2701,7 @@ int srt_levels_build(const srt_comm* comm, int n, int ld, int row0, int nrows, i
     L->l8 = l8;
     L->pkw = pkw;
     L->total = total_x;
+    L->pn_cap = lvl_pn_cap(hist, n, nrows, D);
     L->dkey = dkey; /* the diagonal keys of this rank's rows */
     L->r_rows = r_rows;
     return SRT_OK;
@@ -2549,7 +2719,7 @@ int srt_levels_pkw_ready(void) {
  * and the reliability passes; ties != NULL adds the tied pairs. pred16: predT holds int16 (n <=
  * 32768: half the bytes of the predecessor slab and its transpose), else int32. */
 int srt_levels_pred(void* predT, int pred16, double* rT, size_t ldp, unsigned long long* ties,
-                    hipStream_t st) {
+                    int32_t* pn_over, int* pn_cap, hipStream_t st) {
     /* pred16 == 2: the packed form (srt_levels_rtab) */
     lvl_state* L = &g_lvl[srt_state_slot()];
     if (!L->held) {
@@ -2569,18 +2739,52 @@ int srt_levels_pred(void* predT, int pred16, double* rT, size_t ldp, unsigned lo
         srt_set_error("levels: the packed form needs the reliability table");
         return SRT_E_ARG;
     }
+    /* The Delta_1 groups from the in-arc runs first (lvl_pred_near_kernel), where the runs pay:
+     * a wide share of the sources, as lvl_near_kernel's (the runs are read whole whatever the
+     * share), few levels (a plane row is read per level: the first arc batch, D <= 8) and a
+     * sparse Delta_1 (the histogram's capacity <= 1,024; past that the plane slices are dense
+     * enough to gather). SRT_FORM bcap (the bucket capacity hook of the sparse kernels, which a
+     * level build does not otherwise read; the key budget of SRT_FORM is spent): k > 0 takes
+     * the pre-pass always, with buckets of min(k, 2,048) entries -- 2,048 cannot overflow, a
+     * small k makes the tests' overflowing buckets --, k < 0 never. Not with the tie count: a
+     * tied pair is seen only by walking the whole group. */
+    uint32_t *bkt = NULL, *bcnt = NULL;
+    int cap = 0;
+    *pn_cap = 0;
+    {
+        const int fcap = srt_form_int("bcap", 0);
+        if (fcap > 0)
+            cap = min(fcap, 2048);
+        else if (fcap == 0 && L->nw >= LVL_NEAR_MIN_NW && L->D <= LVL_BATCH && L->pn_cap <= 1024)
+            cap = L->pn_cap;
+        if (ties || !pn_over || L->D < 2 || L->nw > LVL_NEAR_NW) cap = 0;
+    }
+    if (cap) {
+        const size_t units = (size_t)L->n * L->nchunk;
+        int ok = 1; /* no room for the buckets: the walk as it is (pred_near reports 0) */
+        LVL_TRY_ALLOC(bkt, units * cap * sizeof(uint32_t), &ok);
+        LVL_TRY_ALLOC(bcnt, units * sizeof(uint32_t), &ok);
+        if (!ok) bkt = bcnt = NULL, cap = 0;
+    }
+    if (cap) {
+        const size_t lds = 4 * (size_t)(L->nw + L->nchunk) * sizeof(uint32_t);
+        lvl_pred_near_kernel<<<srt_ceil_div(L->n, 4), 256, lds, st>>>(
+            L->n, L->nw, L->nchunk, L->row0, L->nrows, L->D, cap, L->off, L->arcs, L->lev, bkt, bcnt, pn_over);
+        SRT_HIPCHK(hipGetLastError());
+        *pn_cap = cap;
+    }
     if (pred16 == 2)
         lvl_pred_kernel<uint32_t><<<lvl_grid((const void*)lvl_pred_kernel<uint32_t>, L->nblk), 256, 0, st>>>(
             L->n, L->nw, L->nchunk, L->row0, L->nrows, L->D, L->nblk, L->off, L->arcs, L->aoff, L->ar,
-            L->rix, L->lev, (uint32_t*)predT, rT, ldp, part);
+            L->rix, L->lev, (uint32_t*)predT, rT, ldp, part, bkt, bcnt, cap);
     else if (pred16)
         lvl_pred_kernel<int16_t><<<lvl_grid((const void*)lvl_pred_kernel<int16_t>, L->nblk), 256, 0, st>>>(
             L->n, L->nw, L->nchunk, L->row0, L->nrows, L->D, L->nblk, L->off, L->arcs, L->aoff, L->ar,
-            L->rix, L->lev, (int16_t*)predT, rT, ldp, part);
+            L->rix, L->lev, (int16_t*)predT, rT, ldp, part, bkt, bcnt, cap);
     else
         lvl_pred_kernel<int32_t><<<lvl_grid((const void*)lvl_pred_kernel<int32_t>, L->nblk), 256, 0, st>>>(
             L->n, L->nw, L->nchunk, L->row0, L->nrows, L->D, L->nblk, L->off, L->arcs, L->aoff, L->ar,
-            L->rix, L->lev, (int32_t*)predT, rT, ldp, part);
+            L->rix, L->lev, (int32_t*)predT, rT, ldp, part, bkt, bcnt, cap);
     SRT_HIPCHK(hipGetLastError());
     if (ties) {
         lvl_sum_kernel<<<1, 1024, 0, st>>>(part, 1024, ties);
