@@ -99,7 +99,10 @@ typedef struct srt_build_stats {
     int64_t tied_pairs;  /* pairs (s, t), s != t, whose smallest D[s][u] over the tight
                           * predecessors u of t is reached by two or more u: igraph's heap order
                           * picks the reference's predecessor there (topology.c:1679-1701), the
-                          * build takes the smallest u -- the class where reliability can differ */
+                          * build takes the smallest u -- the class where reliability can differ.
+                          * Unreachable pairs are never tied. Sharded builds: each rank of
+                          * srt_dense_build_sharded reports the pairs of its own source rows;
+                          * srt_build_tables_multi / _subset report the sum over the ranks */
     int32_t levels;      /* dense level builds (dist_enc 12): the Dial level that settled every pair */
     int64_t work_bytes;  /* algorithmic bytes of the timed launches (level builds: the Delta words
                           * gathered over all levels, counted on the device -- a unit stops early

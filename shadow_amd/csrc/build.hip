@@ -493,6 +493,8 @@ static void ms_sweep_order(const srt_sparse_graph* g, std::vector<int32_t>& orde
     order.clear();
     order.reserve((size_t)n);
     int tag = 0;
+    std::vector<char> placed((size_t)n, 0);
+    /* over out-arcs, never into a vertex already placed: every vertex is placed exactly once */
     auto bfs = [&](int s, std::vector<int32_t>& out) {
         out.clear();
         out.push_back(s);
@@ -500,20 +502,28 @@ static void ms_sweep_order(const srt_sparse_graph* g, std::vector<int32_t>& orde
         for (size_t h = 0; h < out.size(); h++)
             for (int a = g->h_rp2[out[h]].x; a < g->h_rp2[out[h]].y; a++) {
                 const int v = (int)g->h_cw2[a].x;
-                if (seen[v] != tag) {
+                if (seen[v] != tag && !placed[v]) {
                     seen[v] = tag;
                     out.push_back(v);
                 }
             }
     };
-    std::vector<char> placed((size_t)n, 0);
     for (int v0 = 0; v0 < n; v0++) {
         if (placed[v0]) continue;
         ++tag;
         bfs(v0, q); /* the component of v0; its last vertex is far from v0 */
         const int far = q.back();
+        const size_t reach = q.size();
         ++tag;
         bfs(far, q);
+        /* a directed graph that is not strongly connected: the far end may not lead back, and a
+         * sweep from it would leave v0 unplaced for good (its sources in no cluster, their rows
+         * never written). What the far end reaches is part of what v0 reaches, so a smaller sweep
+         * is one that misses v0: sweep from v0 instead. */
+        if (q.size() < reach) {
+            ++tag;
+            bfs(v0, q);
+        }
         for (int v : q) placed[v] = 1;
         order.insert(order.end(), q.begin(), q.end());
     }

@@ -56,8 +56,10 @@ def test_levels_match_oracle(gpu, monkeypatch, kind):
     reliabilities: by default one target-major word per pair with the level beside it
     (lvl_pred_kernel), one transpose, then rel_pk_kernel, which writes the u32 rows too;
     "transposed" (SRT_FORM pkw=0) keeps the u8 level rows and rel_tree_kernel; "manyrel" (more
-    distinct values than the table holds) takes the f64 rows. "c1like" has distances past 31 quanta: the packed
-    words cannot hold its levels (the transposed form, then the sweeps past 64)."""
+    distinct values than the table holds) takes the f64 rows. "c1like" has distances past 31 quanta
+    (its largest is 56, row eccentricities 32-56): the packed words cannot hold its levels, so it
+    takes the transposed form, every row in level order (the sweeps start past 64;
+    test_gpu_level_edges.py sits on each of these edges)."""
     set_form(monkeypatch, levels="1")
     if kind in ("transposed", "ties_transposed"):
         set_form(monkeypatch, levels="1", pkw="0")
