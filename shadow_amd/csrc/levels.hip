@@ -24,7 +24,11 @@
  * words per vertex. lev[d - 1][j][word] for d = 1..lmax, R[j][word]; one wave owns a (target j,
  * 64-word source chunk) unit, so every arc costs one coalesced 256-B gather of Delta_{d-w}[k].
  * In-arcs come from the rows of w (undirected: row j holds j's in-arcs, and a row-sharded rank has
- * them for its rows) or its columns (directed, one GPU), grouped by (target, weight).
+ * them for its rows) or its columns (directed), grouped by (target, weight). On one GPU the columns
+ * are whole; a row-sharded rank of a directed graph has its rows' part of every column, so the
+ * ranks' parts are gathered and merged on every rank ("directed graph, N > 1" below). After the
+ * extraction every form is the same: each target's in-arcs up to the extracted weight, sorted by
+ * (weight, source), read with the rank's source window.
  */
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
@@ -310,6 +314,147 @@ __global__ void lvl_cnt_gunpack_kernel(int ld, int R, int max_rows, int w0, int 
     const int jj = j - (int)(nb * q / R) * SRT_SHARD_ALIGN;
     const uint16_t* blk = cg + (size_t)q * max_rows * (w1 - w0 + 1);
     for (int w = w0; w <= w1; ++w) cnt[(size_t)j * LVL_STRIDE + w] = blk[(size_t)(w - w0) * max_rows + jj];
+}
+
+/* ---- directed graph, N > 1 --------------------------------------------------------------------- *
+ * A rank holds the out-arcs of its rows, and a target's in-arcs are spread over every rank's
+ * rows. Each rank counts and fills the columns of its own rows (lvl_arcs_colwin_kernel), every
+ * rank's (target, weight) counts are all-gathered (u16, [weight][target]), each rank packs its
+ * arcs of weight <= lw into one block -- its targets in order, the weights in order inside a
+ * target, 4 B of source | weight << 16 and 8 B of reliability per arc -- the blocks are
+ * all-gathered once, padded to the largest rank's, and lvl_dplace_kernel copies every rank's run
+ * of a target into the target's segment of the (target, weight)-major arcs, the ranks in order.
+ * The segmented sort of the one-GPU directed build then orders each segment by (weight, source):
+ * the keys of a segment are distinct, so the result does not depend on where the cursors' atomics
+ * put an arc inside its run. */
+/* Row-window columns form: workgroup = 64 target columns x a chunk of the rank's rows, lane =
+ * column, the four waves sweep the chunk's rows (one coalesced 256-B segment of a row per wave and
+ * step) into a per-workgroup LDS histogram. COUNT adds the histogram to cnt (zeroed before);
+ * FILL takes the chunk's runs from the cursors in cnt (atomically, each (target, weight) run of
+ * the rank is shared by the chunks) and places the arcs in a second sweep. */
+#define LVL_DROWS 256 /* rows per workgroup */
+template <bool FILL>
+__global__ __launch_bounds__(256) void lvl_arcs_colwin_kernel(int n, int ld, int row0, int lrows,
+                                                              const uint32_t* __restrict__ w,
+                                                              int32_t* __restrict__ cnt, int lmax,
+                                                              uint32_t* __restrict__ arcs = nullptr,
+                                                              const double* __restrict__ r = nullptr,
+                                                              double* __restrict__ ar = nullptr) {
+    __shared__ int h[64 * LVL_STRIDE];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int j0 = blockIdx.x * 64, j = j0 + lane;
+    const int k0 = blockIdx.y * LVL_DROWS, k1 = min(lrows, k0 + LVL_DROWS);
+    for (int i = threadIdx.x; i < 64 * LVL_STRIDE; i += 256) h[i] = 0;
+    __syncthreads();
+    const int wmax = FILL ? lmax : LVL_WMAX;
+    if (j < n)
+        for (int kk = k0 + wv; kk < k1; kk += 4) {
+            const uint32_t x = w[(size_t)kk * ld + j];
+            if (row0 + kk != j && x >= 1u && x <= (uint32_t)wmax) atomicAdd(&h[lane * LVL_STRIDE + x], 1);
+        }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 64 * LVL_STRIDE; i += 256) {
+        const int v = h[i];
+        if (!v) continue;
+        int32_t* g = cnt + (size_t)(j0 + i / LVL_STRIDE) * LVL_STRIDE + i % LVL_STRIDE;
+        if (FILL) h[i] = atomicAdd(g, v); /* the chunk's run inside the rank's (target, weight) run */
+        else atomicAdd(g, v);
+    }
+    if (!FILL) return;
+    __syncthreads();
+    if (j < n)
+        for (int kk = k0 + wv; kk < k1; kk += 4) {
+            const uint32_t x = w[(size_t)kk * ld + j];
+            if (row0 + kk != j && x >= 1u && x <= (uint32_t)wmax) {
+                const int p = atomicAdd(&h[lane * LVL_STRIDE + x], 1);
+                arcs[p] = (uint32_t)(row0 + kk) | (x << 16);
+                ar[p] = r[(size_t)kk * ld + j];
+            }
+        }
+}
+/* this rank's arcs per weight (its own histogram, before the exchange sums it) into its slot of
+ * the exchange as 16-bit halves: every weight, so both extractions' block sizes come from it */
+__global__ void lvl_drank_counts_kernel(const unsigned long long* __restrict__ hist, int32_t* __restrict__ slot) {
+    const int w = threadIdx.x;
+    if (w < 1 || w >= LVL_STRIDE) return;
+    const uint32_t t = (uint32_t)hist[w];
+    slot[2 * w] = (int32_t)(t & 0xFFFFu);
+    slot[2 * w + 1] = (int32_t)(t >> 16);
+}
+/* every rank's (target, weight) counts, as gathered: weights 1..wa in a ([rank][weight][target]),
+ * weights wa + 1..wb in b (the second extraction's; NULL before it) */
+struct lvl_dcnt {
+    const uint16_t* a;
+    const uint16_t* b;
+    int wa, wb, ld;
+    __device__ __forceinline__ int at(int q, int w, int j) const {
+        return w <= wa ? a[((size_t)q * wa + (w - 1)) * ld + j]
+                       : b[((size_t)q * (wb - wa) + (w - wa - 1)) * ld + j];
+    }
+};
+/* this rank's counts of the weights w0..w1 into its block ([weight][target], u16: a rank holds
+ * fewer than 65,536 rows) */
+__global__ void lvl_dcnt_pack_kernel(int ld, int w0, int w1, const int32_t* __restrict__ cnt,
+                                     uint16_t* __restrict__ blk) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= ld) return;
+    for (int w = w0; w <= w1; ++w) blk[(size_t)(w - w0) * ld + j] = (uint16_t)cnt[(size_t)j * LVL_STRIDE + w];
+}
+/* the global counts of the weights w0..w1: the ranks' blocks summed */
+__global__ void lvl_dcnt_sum_kernel(int ld, int R, int w0, int w1, const uint16_t* __restrict__ cg,
+                                    int32_t* __restrict__ cnt) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= ld) return;
+    const int nwt = w1 - w0 + 1;
+    for (int w = w0; w <= w1; ++w) {
+        int s = 0;
+        for (int q = 0; q < R; ++q) s += cg[((size_t)q * nwt + (w - w0)) * ld + j];
+        cnt[(size_t)j * LVL_STRIDE + w] = s;
+    }
+}
+/* tq[q (ld + 1) + j]: rank q's arcs of weight <= lw into target j (0 at j == ld and at the end);
+ * its exclusive scan gives every run's start inside rank q's block (less the scan at j == 0) */
+__global__ void lvl_dtot_kernel(int R, int lw, lvl_dcnt dc, int32_t* __restrict__ tq) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nt = (size_t)R * (dc.ld + 1);
+    if (i > nt) return;
+    const int q = (int)(i / (size_t)(dc.ld + 1)), j = (int)(i % (size_t)(dc.ld + 1));
+    int t = 0;
+    if (i < nt && j < dc.ld)
+        for (int w = 1; w <= lw; ++w) t += dc.at(q, w, j);
+    tq[i] = t;
+}
+/* the fill's cursors: the start of this rank's (target, weight) runs inside its block */
+__global__ void lvl_dcur_kernel(int me, int lw, lvl_dcnt dc, const int32_t* __restrict__ oq,
+                                int32_t* __restrict__ cur) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= dc.ld) return;
+    const size_t b = (size_t)me * (dc.ld + 1);
+    int run = oq[b + j] - oq[b];
+    for (int w = 1; w <= lw; ++w) {
+        cur[(size_t)j * LVL_STRIDE + w] = run;
+        run += dc.at(me, w, j);
+    }
+}
+/* the gathered blocks (rank q's at wire + q * blk bytes: blk / 12 arcs, then their f64s) into the
+ * (target, weight)-major arcs: a wave per target, the ranks' runs one after the other */
+__global__ void lvl_dplace_kernel(int n, int ld, int R, size_t blk, const int32_t* __restrict__ off,
+                                  const int32_t* __restrict__ tq, const int32_t* __restrict__ oq,
+                                  const char* __restrict__ wire, uint32_t* __restrict__ arcs,
+                                  double* __restrict__ ar) {
+    const int j = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (j >= n) return;
+    int dst = off[(size_t)j * LVL_STRIDE];
+    for (int q = 0; q < R; ++q) {
+        const size_t b = (size_t)q * (ld + 1);
+        const int c = tq[b + j], s = oq[b + j] - oq[b];
+        const uint32_t* wa = reinterpret_cast<const uint32_t*>(wire + (size_t)q * blk);
+        const double* wr = reinterpret_cast<const double*>(wire + (size_t)q * blk + blk / 3);
+        for (int i = lane; i < c; i += 64) {
+            arcs[dst + i] = wa[s + i];
+            ar[dst + i] = wr[s + i];
+        }
+        dst += c;
+    }
 }
 
 /* ---- the arcs' distinct reliabilities (packed post pass) ------------------------------------ *
@@ -744,6 +889,10 @@ __global__ __launch_bounds__(256) void lvl_offsets_kernel(int ld, int lw, int R,
 #define LVL_X_LIMBS (2 * LVL_STRIDE + 2)
 #define LVL_X_CNT (2 * LVL_BATCH)
 static size_t lvl_x_words(int R) { return LVL_X_LIMBS + (size_t)R * LVL_X_CNT + (size_t)R * (LVL_RT_CAP + 1) * 2; }
+/* directed, N > 1: the limbs and the failure count, then every rank's arcs per weight, all 256
+ * weights as 16-bit halves (both extractions' block sizes); no reliability blocks (no stash) */
+#define LVL_X_DCNT (2 * LVL_STRIDE)
+static size_t lvl_xd_words(int R) { return LVL_X_LIMBS + (size_t)R * LVL_X_DCNT; }
 /* per rank q in [q0, q1) and weight w <= LVL_BATCH: its shard's arcs of weight w, into the
  * exchange as 16-bit halves (a rank counts its own shard; a solo rank every shard of its
  * synthesised counts) */
@@ -1908,8 +2057,9 @@ __global__ void lvl_vote_kernel(const int* __restrict__ inc_last,
     vote[3] = (int32_t)(s >> 42);
 }
 
-/* One build of the local rows' distances (nrows x ld). comm (NULL on one GPU): undirected row
- * shards, every rank sees every target's in-arcs after the segment broadcasts. fw_ms: the
+/* One build of the local rows' distances (nrows x ld). comm (NULL on one GPU): row
+ * shards, every rank sees every target's in-arcs after the segment broadcasts (undirected) or the
+ * all-gather of the ranks' blocks (directed). fw_ms: the
  * predicted Floyd-Warshall time (of the largest shard); the level budget keeps the predicted level
  * time under half of it. *levels = the level that settled every pair (0: not applicable / over
  * budget / out of memory -- the caller runs Floyd-Warshall). *gather_bytes: the Delta words
@@ -1934,7 +2084,24 @@ __global__ void lvl_vote_kernel(const int* __restrict__ inc_last,
  *   5. per batch of levels (1-5, then 6, 7, 8 one at a time, then 8 at a time) the vote
  *      (sum); after the batch ending at lx < lmax, extract(lmax) as in 4's second form.
  * The vote's "all done" is the verdict. tests/test_dist_gloo.py rehearses this sequence over gloo
- * and tests/test_gpu_protocol.py checks every rank's collective log (srt_comm_log_*) against it. */
+ * and tests/test_gpu_protocol.py checks every rank's collective log (srt_comm_log_*) against it.
+ *
+ * Directed graph, N > 1 (a timing-only communicator keeps the FW, decided before any collective):
+ * the same order with its own blocks, never streamed (stream_ok stays 0):
+ *   1. the exchange (lvl_xd_words): the limbs of the histogram of this rank's rows' arcs (the sum
+ *      is the global histogram), the failure count, and every rank's arcs per weight for all 256
+ *      weights -- the block sizes of both extractions, so neither needs a read-back; no
+ *      reliability blocks (there is no stash for the columns form);
+ *   2. the agreement, as above; every buffer of the path is in the arenas it covers;
+ *   3. every rank's (target, weight <= lx) counts: one all-gather of u16 blocks [weight][target]
+ *      over all ld targets; their sum is the global count, and the parts stay for the placement;
+ *   4. the arcs of weight <= lx: one all-gather of every rank's block (12 B per arc: source |
+ *      weight << 16, then the f64 reliabilities; padded to the largest rank's arcs, made even),
+ *      lvl_dplace_kernel, the segmented sort, the rank-local reliability table;
+ *   5. the votes as above; after the batch ending at lx < lmax, 3 for the weights lx + 1..lmax and
+ *      4 for every arc of weight <= lmax.
+ * tests/levels_protocol_directed.py restates it and tests/test_gpu_directed_ranks.py checks every
+ * rank's log against that. */
 int srt_levels_build(const srt_comm* comm, int n, int ld, int row0, int nrows, int directed,
                      const uint32_t* w_rows, const double* r_rows, uint32_t* lat_rows, double fw_ms,
                      hipStream_t st, evpool_t* evp, int* levels, int64_t* gather_bytes) {
@@ -1947,7 +2114,10 @@ int srt_levels_build(const srt_comm* comm, int n, int ld, int row0, int nrows, i
      * 128 == 0 on every rank once ld % 128 == 0; the 32-bit plane offsets are checked against the
      * largest shard */
     if (n > 65535 || ld % 128 || nrows % 128 || row0 % 128 || R > 64) return SRT_OK;
-    if (R > 1 && directed) return SRT_OK; /* in-arcs of a directed graph span every rank's rows */
+    /* directed, N > 1: the extraction of the header's "directed graph, N > 1" section; a
+     * timing-only communicator has no synthesis for it and keeps the FW (before any collective) */
+    const bool dr = R > 1 && directed;
+    if (dr && srt_comm_is_solo(comm)) return SRT_OK;
     int max_rows = nrows;
     for (int q = 0; q < R && R > 1; q++) {
         int32_t b = 0, e = 0;
@@ -2004,7 +2174,7 @@ int srt_levels_build(const srt_comm* comm, int n, int ld, int row0, int nrows, i
         a1.add(&stash, (size_t)nrows * LVL_STASH_CAP * sizeof(uint32_t));
         a1.add(&scnt, (size_t)nrows * 4 * sizeof(int32_t));
     }
-    const size_t xn = R > 1 ? lvl_x_words(R) : 0;
+    const size_t xn = dr ? lvl_xd_words(R) : R > 1 ? lvl_x_words(R) : 0;
     if (R > 1) a1.add(&xbuf, xn * sizeof(int32_t));
     commit(a1, &ok);
     constexpr size_t LVL_GB = LVL_RT_CAP + 1;
@@ -2013,7 +2183,11 @@ int srt_levels_build(const srt_comm* comm, int n, int ld, int row0, int nrows, i
     int32_t* const xblk = xbuf ? xcnt + (size_t)R * LVL_X_CNT : NULL; /* R blocks of LVL_GB u64 */
     if (ok) {
         SRT_HIPCHK(hipMemsetAsync(cnt, 0, (ncnt + 1) * sizeof(int32_t), st));
-        if (directed)
+        if (dr) { /* this rank's rows' contribution to every target's counts */
+            if (lrows > 0)
+                lvl_arcs_colwin_kernel<false><<<dim3(ld / 64, srt_ceil_div(lrows, LVL_DROWS)), 256, 0, st>>>(
+                    n, ld, row0, lrows, w_rows, cnt, 0);
+        } else if (directed)
             lvl_arcs_cols_kernel<false><<<ld / 64, 256, 0, st>>>(n, ld, w_rows, cnt, 0, NULL, NULL);
         else
             lvl_arcs_rows_kernel<false><<<nrows, 256, 0, st>>>(n, ld, row0, w_rows, cnt, 0, NULL, NULL,
@@ -2023,7 +2197,7 @@ int srt_levels_build(const srt_comm* comm, int n, int ld, int row0, int nrows, i
         /* this rank's rows (a solo rank: every row of its synthesised counts, which are its own
          * rows' n / lrows times over when that divides) */
         const bool rep = solo && lrows > 0 && lrows == nrows && n % lrows == 0;
-        const bool own = R > 1 && (!solo || rep);
+        const bool own = R > 1 && !dr && (!solo || rep); /* (directed: every target's row) */
         lvl_hist_kernel<<<own ? 256 : 1024, 256, 0, st>>>(own ? (size_t)(rep ? lrows : nrows) * LVL_STRIDE : ncnt,
                                                          own ? cnt + (size_t)row0 * LVL_STRIDE : cnt, dhist,
                                                          rep ? (unsigned)(n / lrows) : 1u);
@@ -2031,7 +2205,10 @@ int srt_levels_build(const srt_comm* comm, int n, int ld, int row0, int nrows, i
         if (R > 1) {
             SRT_HIPCHK(hipMemsetAsync(xbuf, 0, xn * sizeof(int32_t), st));
             lvl_hist_limbs_kernel<<<1, LVL_STRIDE, 0, st>>>(1, dhist, xlimbs);
-            lvl_rank_counts_kernel<<<dim3(LVL_BATCH, solo ? R : 1), 256, 0, st>>>(n, ld, R, solo ? 0 : me, cnt, xcnt);
+            if (dr)
+                lvl_drank_counts_kernel<<<1, LVL_STRIDE, 0, st>>>(dhist, xcnt + (size_t)me * LVL_X_DCNT);
+            else
+                lvl_rank_counts_kernel<<<dim3(LVL_BATCH, solo ? R : 1), 256, 0, st>>>(n, ld, R, solo ? 0 : me, cnt, xcnt);
             if (!directed && lrows > 0) { /* this rank's distinct light reliabilities, its block */
                 int32_t* hd = xblk + (size_t)me * LVL_GB * 2;
                 SRT_HIPCHK(hipMemsetAsync(H, 0xFF, LVL_RT_SLOTS * sizeof(unsigned long long), st));
@@ -2084,7 +2261,7 @@ int srt_levels_build(const srt_comm* comm, int n, int ld, int row0, int nrows, i
      * host time on the critical path. A solo rank's peers hold its own values (their rows are
      * shifted copies of its rows), so it pays the same. */
     std::vector<unsigned long long> u;
-    bool fit = R > 1;
+    bool fit = R > 1 && !dr; /* (the directed exchange carries no reliability blocks) */
     if (fit) {
         size_t all = 0;
         for (int q = 0; q < R && fit; q++) {
@@ -2145,6 +2322,12 @@ int srt_levels_build(const srt_comm* comm, int n, int ld, int row0, int nrows, i
     uint8_t* done = NULL;
     size_t tmp_bytes = 0, sb = 0;
     SRT_HIPCHK(hipcub::DeviceScan::ExclusiveSum(NULL, tmp_bytes, cnt, off, (int)(ncnt + 1), st));
+    const size_t dnt = (size_t)R * ((size_t)ld + 1) + 1; /* directed, N > 1: the runs' totals */
+    if (dr) {
+        size_t tb2 = 0;
+        SRT_HIPCHK(hipcub::DeviceScan::ExclusiveSum(NULL, tb2, cnt, off, (int)dnt, st));
+        tmp_bytes = max(tmp_bytes, tb2);
+    }
     const bool need_sort_own = total_own > 0 && !(!directed && lmax_own <= LVL_STASH_W && hist[0] == 0);
     if (need_sort_own)
         SRT_HIPCHK(hipcub::DeviceSegmentedRadixSort::SortPairs(NULL, sb, arcs, arcs2, ar, ar2, total_own,
@@ -2175,12 +2358,36 @@ int srt_levels_build(const srt_comm* comm, int n, int ld, int row0, int nrows, i
     /* N > 1: the segments' reliability blocks (extract()), the counts' all-gather blocks (u16,
      * every weight up to the budget), and the streamed wire's offsets at the shard starts */
     double* gat = NULL;
-    if (total_own > 0 && n <= 32768 && R > 1) a2.add(&gat, (size_t)R * LVL_GB * sizeof(double));
+    if (total_own > 0 && n <= 32768 && R > 1 && !dr) a2.add(&gat, (size_t)R * LVL_GB * sizeof(double));
     uint16_t* cg = NULL;
     int32_t* packed = NULL;
-    if (R > 1) {
+    if (R > 1 && !dr) {
         a2.add(&cg, ((size_t)R * max_rows * max(lmax_own, 1) + 8) * sizeof(uint16_t));
         a2.add(&packed, (size_t)4 * LVL_BATCH * 65 * sizeof(int32_t));
+    }
+    /* directed, N > 1: every rank's (target, weight <= budget) counts, the runs' totals and their
+     * scan, the fill's cursors, and the gathered blocks of arcs (12 B per arc, every rank's block
+     * padded to the largest; the ranks' arcs per weight are in the exchange) */
+    int32_t *tq = NULL, *oq = NULL, *dcur = NULL;
+    char* dwire = NULL;
+    auto dblock = [&](int lw) -> size_t { /* arcs of the largest rank's block, even */
+        uint64_t mx = 0;
+        for (int q = 0; q < R; q++) {
+            uint64_t t = 0;
+            for (int x = 1; x <= lw; ++x) {
+                const int32_t* c = hx + LVL_X_LIMBS + (size_t)q * LVL_X_DCNT + 2 * x;
+                t += (uint32_t)c[0] | ((uint32_t)c[1] << 16);
+            }
+            mx = t > mx ? t : mx;
+        }
+        return (size_t)((mx + 1) & ~(uint64_t)1);
+    };
+    if (dr) {
+        a2.add(&cg, ((size_t)R * ld * max(lmax_own, 1) + 8) * sizeof(uint16_t));
+        a2.add(&tq, dnt * sizeof(int32_t));
+        a2.add(&oq, dnt * sizeof(int32_t));
+        a2.add(&dcur, (ncnt + 1) * sizeof(int32_t));
+        a2.add(&dwire, (size_t)R * dblock(lmax_own) * 12 + 16);
     }
     commit(a2, &ok);
     /* the streamed first extraction's wire (extract_streamed): every rank's block of a weight
@@ -2289,8 +2496,22 @@ int srt_levels_build(const srt_comm* comm, int n, int ld, int row0, int nrows, i
      * it uses. The counts stay whole (narrow offsets) for the second extraction. */
     const int lx = min(lmax, LVL_BATCH);
     /* every target's counts of weights w0..w1 on every rank (a solo rank has them: synthesised) */
+    lvl_dcnt dcn{NULL, NULL, 0, 0, ld}; /* directed, N > 1: the gathered per-rank counts */
     auto share_counts = [&](int w0, int w1) -> int {
         if (R == 1 || w1 < w0) return SRT_OK;
+        if (dr) { /* every rank's contribution to every target: summed, and kept per rank (dcnt) */
+            const size_t dblk = (size_t)ld * (w1 - w0 + 1);
+            uint16_t* reg = cg + (size_t)R * ld * (w0 - 1); /* weights 1..lx, then lx + 1..lmax */
+            lvl_dcnt_pack_kernel<<<srt_ceil_div(ld, 256), 256, 0, st>>>(ld, w0, w1, cnt, reg + (size_t)me * dblk);
+            SRT_HIPCHK(hipGetLastError());
+            int rc_ = srt_coll_allgather(comm, reg, dblk * sizeof(uint16_t), st);
+            if (rc_) return rc_;
+            lvl_dcnt_sum_kernel<<<srt_ceil_div(ld, 256), 256, 0, st>>>(ld, R, w0, w1, reg, cnt);
+            SRT_HIPCHK(hipGetLastError());
+            if (w0 == 1) dcn = lvl_dcnt{reg, NULL, w1, w1, ld};
+            else dcn.b = reg, dcn.wb = w1;
+            return SRT_OK;
+        }
         const size_t blk = (size_t)max_rows * (w1 - w0 + 1);
         if (nrows > 0)
             lvl_cnt_gpack_kernel<<<srt_ceil_div(nrows, 256), 256, 0, st>>>(row0, nrows, max_rows, w0, w1, me,
@@ -2330,14 +2551,28 @@ int srt_levels_build(const srt_comm* comm, int n, int ld, int row0, int nrows, i
         const int sorted_w = !directed && lw <= LVL_STASH_W && hist[0] == 0; /* global values */
         int rc_ = offsets(lw); /* (target, weight <= lw)-major */
         if (rc_) return rc_;
-        if (directed)
+        if (dr) { /* this rank's arcs into its block, the blocks all-gathered once, then placed */
+            const size_t blk = dblock(lw) * 12; /* (from the exchange: alike on every rank) */
+            lvl_dtot_kernel<<<(unsigned)((dnt + 255) / 256), 256, 0, st>>>(R, lw, dcn, tq);
+            SRT_HIPCHK(hipGetLastError());
+            SRT_HIPCHK(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, tq, oq, (int)dnt, st));
+            lvl_dcur_kernel<<<srt_ceil_div(ld, 256), 256, 0, st>>>(me, lw, dcn, oq, dcur);
+            char* mine = dwire + (size_t)me * blk;
+            if (lrows > 0)
+                lvl_arcs_colwin_kernel<true><<<dim3(ld / 64, srt_ceil_div(lrows, LVL_DROWS)), 256, 0, st>>>(
+                    n, ld, row0, lrows, w_rows, dcur, lw, reinterpret_cast<uint32_t*>(mine), r_rows,
+                    reinterpret_cast<double*>(mine + blk / 3));
+            SRT_HIPCHK(hipGetLastError());
+            if ((rc_ = srt_coll_allgather(comm, dwire, blk, st))) return rc_;
+            lvl_dplace_kernel<<<srt_ceil_div(n, 4), 256, 0, st>>>(n, ld, R, blk, off, tq, oq, dwire, arcsA, arA);
+        } else if (directed)
             lvl_arcs_cols_kernel<true><<<ld / 64, 256, 0, st>>>(n, ld, w_rows, NULL, lw, off, arcsA,
                                                                 r_rows, arA);
         else
             lvl_arcs_rows_kernel<true><<<nrows, 256, 0, st>>>(n, ld, row0, w_rows, NULL, lw, off, arcsA,
                                                               r_rows, arA, NULL, stash, scnt);
         SRT_HIPCHK(hipGetLastError());
-        if (R > 1) { /* every rank filled its rows' segment: broadcast the segments */
+        if (R > 1 && !dr) { /* every rank filled its rows' segment: broadcast the segments */
             int32_t hoff[65];
             for (int q = 0; q <= R; q++) {
                 int32_t b = ld, e = ld;

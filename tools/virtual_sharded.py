@@ -10,7 +10,13 @@ the symmetry exchange -- at the bench workload's full size, where offsets and bu
 largest. The ranks share the GPU, so the time is total work plus schedule overhead, not a scaling
 number (the N-GPU runs are the driver's). Sampled rows are checked against the C oracle.
 
-usage: python tools/virtual_sharded.py [--workload c4] [--ranks 2] [--rows 3]
+--directed N builds a directed complete graph of N vertices instead (weights 1..16 quanta,
+independent per direction, reliabilities from a grid of 300 values, made on the device): the
+row-sharded directed level build against the Floyd-Warshall (SRT_FORM levels=0, or an older
+library through SRT_LIB_PATH). No oracle at that size: the line carries a checksum of the latency
+table and the sum of the reliabilities, to be compared between the two runs.
+
+usage: python tools/virtual_sharded.py [--workload c4] [--ranks 2] [--rows 3] [--directed N]
 """
 import argparse
 import ctypes
@@ -41,11 +47,13 @@ def main():
     ap.add_argument("--ranks", type=int, default=2)
     ap.add_argument("--rows", type=int, default=3, help="sampled rows checked against the oracle")
     ap.add_argument("--sym", default=None, help="SRT_FORM sym override (0: all-tile rounds)")
+    ap.add_argument("--directed", type=int, default=0, metavar="N",
+                    help="a directed complete graph of N vertices, weights 1..16 quanta")
     a = ap.parse_args()
     if a.sym is not None:
         os.environ["SRT_FORM"] = f"sym={a.sym}"
     wl = WORKLOADS[a.workload]
-    n, R = wl["n"], a.ranks
+    n, R = a.directed or wl["n"], a.ranks
     L = _lib.lib()
     ld = (n + 127) // 128 * 128
     comms = (ctypes.c_void_p * R)()
@@ -61,7 +69,17 @@ def main():
         lat = torch.empty_like(w)
         rel = torch.empty_like(rr)
         st = torch.cuda.Stream()
-        if e > b:
+        if a.directed:
+            gen = torch.Generator(device="cuda").manual_seed(41 + r)
+            w[:] = torch.randint(1, 17, (nr, ld), generator=gen, device="cuda", dtype=torch.int32)
+            loss = torch.randint(0, 300, (nr, ld), generator=gen, device="cuda")
+            rr[:] = 1.0 - loss.double() / 10000.0
+            rows = torch.arange(b, b + nr, device="cuda").unsqueeze(1)
+            cols = torch.arange(ld, device="cuda").unsqueeze(0)
+            pad = (rows >= n) | (cols >= n)
+            w[pad] = 0x7FFFFFFF
+            rr[pad] = 0.0
+        elif e > b:
             _lib.check(L.srt_gen_complete_device(n, ld, b, e - b, wl["seed"], wl["lat_max"],
                                                  wl["self_max"], wl["loss_max"], w.data_ptr(),
                                                  rr.data_ptr(), ctypes.c_void_p(st.cuda_stream)),
@@ -77,14 +95,14 @@ def main():
         L.srt_virtual_rank_bind(r, 0)
         w, rr, lat, rel = bufs[r]
         stats[r].time_kernels = 0
-        rcs[r] = L.srt_dense_build_sharded(ctypes.c_void_p(comms[r]), n, ld, 0, w.data_ptr(),
-                                           rr.data_ptr(), lat.data_ptr(), rel.data_ptr(),
+        rcs[r] = L.srt_dense_build_sharded(ctypes.c_void_p(comms[r]), n, ld, int(bool(a.directed)),
+                                           w.data_ptr(), rr.data_ptr(), lat.data_ptr(), rel.data_ptr(),
                                            ctypes.c_void_p(streams[r].cuda_stream), 0,
                                            ctypes.byref(stats[r]))
         L.srt_virtual_rank_bind(-1, 0)
 
     times = []
-    for rep in range(2):
+    for rep in range(4 if a.directed else 2):
         th = [threading.Thread(target=work, args=(r,)) for r in range(R)]
         t0 = time.perf_counter()
         for t in th:
@@ -95,6 +113,22 @@ def main():
         times.append(time.perf_counter() - t0)
         for r in range(R):
             _lib.check(rcs[r], f"rank {r}")
+    if a.directed:
+        lat_sum = sum(int(bufs[r][2][:, :n].to(torch.int64).sum()) for r in range(R))
+        rel_sum = sum(float(bufs[r][3][:, :n].sum()) for r in range(R))
+        print(json.dumps({"graph": "directed complete, w 1..16", "n": n, "virtual_ranks": R,
+                          "lib": os.path.basename(_lib.LIB_PATH), "form": os.environ.get("SRT_FORM", ""),
+                          "dist_enc": [int(s.dist_enc) for s in stats],
+                          "levels": [int(s.levels) for s in stats],
+                          "ms_per_build_wall": round(min(times) * 1e3, 2),
+                          "ms_dist_rank0": round(float(stats[0].ms_fw), 3),
+                          "ms_post_rank0": round(float(stats[0].ms_post), 3),
+                          "lat_sum": lat_sum, "rel_sum": rel_sum,
+                          "note": "virtual ranks share one GPU: a ratio between forms, not a per-rank time"}),
+              flush=True)
+        for r in range(R):
+            L.srt_comm_free(ctypes.c_void_p(comms[r]))
+        return
     import oracle  # test infrastructure: the checker only
     srcs = np.unique(np.linspace(0, n - 1, a.rows).astype(np.int32))
     clat, crel, _, _ = oracle.complete_sample(n, wl["seed"], wl["lat_max"], wl["self_max"],
