@@ -230,6 +230,54 @@ int srt_sparse_graph_rows_list(const srt_sparse_graph* g, int32_t nsrc, const in
                                void* stream, srt_build_stats* stats);
 void srt_sparse_graph_free(srt_sparse_graph* g);
 
+/* ---- routes: which way the paths go (routes.hip) ------------------------------------------
+ * One optional pass over finished distance rows, whichever build made them. Per source s and
+ * target t, three int32 values:
+ *   pred[s][t]  the canonical predecessor, argmin (D[s][u], u) over the tight in-arcs u -> t
+ *               (D[s][s] taken as 0); -1 for t == s and for unreachable t
+ *   first[s][t] the first vertex after s on the path (the forwarding-table entry): t itself
+ *               when pred == s, -1 where pred is -1
+ *   hops[s][t]  the edges on the path: 0 for t == s, -1 for unreachable t
+ * Following pred from t back to s gives the reference's `path:` (topology.c:1322, :1368-1369);
+ * the reliability tables equal the left-to-right product of the arcs' reliabilities along it.
+ * The routes of the path-to-self rule on the diagonal are not exported. */
+typedef struct srt_route_stats {
+    double ms_tables;    /* distance rows (whatever build made them); srt_build_routes only */
+    double ms_routes;    /* HIP events around the route pass alone (dense: the essential-arc
+                          * compaction included) */
+    int64_t ess_arcs;    /* dense: essential arcs compacted */
+    int32_t max_hops;    /* deepest route over the rows of the call */
+    int32_t stage_forms; /* bit f-1 set when some row took staging form f */
+} srt_route_stats;
+
+/* Largest n whose distance row is staged on chip in form 1 (u32 row in LDS) or 2 (u16 row in LDS:
+ * rows that do not fit as u32 and whose finite entries are all below 0xFFFF); form 3 reads the row
+ * from global memory, and its value is the largest n the pass takes at all. */
+int srt_routes_stage_max_n(int form);
+/* Device entry points: every pointer is a device pointer, any of the three outputs may be NULL,
+ * outputs have row stride ldo (>= n; columns >= n are never written), `stream` as above. The
+ * calls return after their work on the stream has finished.
+ * Rows of a sparse graph: row i (of lat_rows, stride ldl, and of the outputs) belongs to srcs[i],
+ * or src_begin + i when srcs is NULL. SRT_E_RANGE for a graph whose distances need u64 rows. */
+int srt_routes_rows_device(const srt_sparse_graph* g, int32_t nsrc, const int32_t* srcs,
+                           int32_t src_begin, const uint32_t* lat_rows, size_t ldl,
+                           int32_t* pred, int32_t* first, int32_t* hops, size_t ldo,
+                           void* stream, srt_route_stats* stats);
+/* Rows [row0, row0 + nrows) of a dense device graph and its finished lat table (both ld x ld, as
+ * for srt_dense_build_device): output row i belongs to source row0 + i. */
+int srt_routes_dense_device(int32_t n, int32_t ld, int32_t directed, const uint32_t* w,
+                            const uint32_t* lat, int32_t row0, int32_t nrows, int32_t* pred,
+                            int32_t* first, int32_t* hops, size_t ldo, void* stream,
+                            srt_route_stats* stats);
+/* Routes of nsrc sources (srcs strictly increasing; NULL with nsrc = n: every vertex) towards
+ * every vertex: host outputs nsrc x n, any of them NULL. One GPU. The distance rows come from
+ * the table build's own choice of algorithm, the routes from the pass above in every case.
+ * use_shortest_path = 0: pred = s, first = t, hops = 1 for every t != s (SRT_E_INVALID unless the
+ * graph is complete, as the table build). */
+int srt_build_routes(const srt_edges* g, const srt_build_opts* opts, int32_t nsrc,
+                     const int32_t* srcs, int32_t* pred, int32_t* first_hop, int32_t* hops,
+                     srt_route_stats* stats);
+
 /* ---- multi-GPU (one process per GPU; RCCL over xGMI) ----------------------------------- */
 typedef struct srt_comm srt_comm;
 /* 128-byte RCCL unique id, created on rank 0 and shared by the caller (e.g. torch.distributed). */

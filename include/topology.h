@@ -113,6 +113,29 @@ int srt_topology_send_packets_ip(Topology* top, int64_t count, const uint32_t* s
                                  const uint32_t* dstIpNet, const double* chance,
                                  const uint8_t* bootstrapping, const uint64_t* payloadLength,
                                  uint8_t* delivered, uint64_t* delayNs);
+/* ---- routes (the reference's `path:` log field; routes.hip) -------------------------------
+ * The canonical shortest path from vertex s to vertex t in s's own row: returns the number of
+ * vertices on it (hops + 1; 1 when s == t), writes the first min(cap, count) of them starting at
+ * s; SRT_E_NOPATH when t is unreachable, SRT_E_ARG for a bad vertex, SRT_E_DEVICE when the route
+ * build failed (logged). The route is always the SOURCE's own row, whichever row the pair cache
+ * serves: when srt_topology_path_source_ip names the other end, the served latency and
+ * reliability belong to route(t, s). A route query records no pair-order lookup, touches no packet
+ * counter or path count and offers nothing to the runahead hook. Predecessor rows are kept per
+ * source vertex until topology_free; a miss builds the asked source together with every attached
+ * vertex that has no row yet (within 1 GiB of rows, else the asked source alone). */
+int32_t srt_topology_route(Topology* top, int32_t s, int32_t t, int32_t* verts, int32_t cap);
+/* the same between attached addresses; SRT_E_UNATTACHED as the lookups */
+int32_t srt_topology_route_ip(Topology* top, uint32_t srcIpNet, uint32_t dstIpNet,
+                              int32_t* verts, int32_t cap);
+/* The reference's `path:` field for that route (topology.c:1322, :1368-1369): the source's id,
+ * then per hop "<--[latency ms,loss]-->id" ("--[" on directed graphs), each hop's edge the
+ * canonical arc of its vertex pair (minimum latency, then lowest edge index). snprintf semantics:
+ * returns the length needed, writes at most cap bytes with the terminator; a negative SRT_E_* code
+ * on failure. */
+int64_t srt_topology_route_string_ip(Topology* top, uint32_t srcIpNet, uint32_t dstIpNet,
+                                     char* buf, size_t cap);
+/* srt_build_routes calls this topology has made (diagnostic: rows are built once) */
+int32_t srt_topology_route_builds(Topology* top);
 /* Graph facts established by validation (topology.c:659-716). */
 int32_t srt_topology_vertex_count(Topology* top);
 int64_t srt_topology_edge_count(Topology* top);

@@ -79,6 +79,16 @@ class BuildStats(ctypes.Structure):
     ]
 
 
+class RouteStats(ctypes.Structure):
+    _fields_ = [
+        ("ms_tables", ctypes.c_double),
+        ("ms_routes", ctypes.c_double),
+        ("ess_arcs", ctypes.c_int64),
+        ("max_hops", ctypes.c_int32),
+        ("stage_forms", ctypes.c_int32),
+    ]
+
+
 # (name, restype, argtypes) for every exported symbol of the C-ABI
 _VP, _I32, _I64, _U32, _U64, _D, _CP = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
                                          ctypes.c_uint32, ctypes.c_uint64, ctypes.c_double,
@@ -107,6 +117,12 @@ SIGNATURES = {
     "srt_sparse_graph_rows": (ctypes.c_int, [_VP, _I32, _I32, _VP, _VP, _VP, _VP]),
     "srt_sparse_graph_rows_list": (ctypes.c_int, [_VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP]),
     "srt_sparse_graph_free": (None, [_VP]),
+    "srt_routes_stage_max_n": (ctypes.c_int, [ctypes.c_int]),
+    "srt_routes_rows_device": (ctypes.c_int, [_VP, _I32, _VP, _I32, _VP, ctypes.c_size_t, _VP, _VP,
+                                               _VP, ctypes.c_size_t, _VP, _VP]),
+    "srt_routes_dense_device": (ctypes.c_int, [_I32, _I32, _I32, _VP, _VP, _I32, _I32, _VP, _VP, _VP,
+                                                ctypes.c_size_t, _VP, _VP]),
+    "srt_build_routes": (ctypes.c_int, [_VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP]),
     "srt_comm_unique_id": (ctypes.c_int, [_VP]),
     "srt_comm_init": (ctypes.c_int, [_VP, _I32, _I32, _I32, _VP]),
     "srt_comm_init_all": (ctypes.c_int, [_I32, _VP, _VP]),
@@ -163,6 +179,10 @@ SIGNATURES = {
                                                    _U64, _VP]),
     "srt_topology_send_packets_ip": (ctypes.c_int, [_VP, ctypes.c_int64, _VP, _VP, _VP, _VP, _VP,
                                                     _VP, _VP]),
+    "srt_topology_route": (_I32, [_VP, _I32, _I32, _VP, _I32]),
+    "srt_topology_route_ip": (_I32, [_VP, _U32, _U32, _VP, _I32]),
+    "srt_topology_route_string_ip": (_I64, [_VP, _U32, _U32, _VP, ctypes.c_size_t]),
+    "srt_topology_route_builds": (_I32, [_VP]),
     "srt_topology_vertex_count": (_I32, [_VP]),
     "srt_topology_edge_count": (_I64, [_VP]),
     "srt_topology_is_directed": (ctypes.c_int, [_VP]),

@@ -2158,3 +2158,220 @@ extern "C" int srt_build_tables_multi(const srt_edges* g, const srt_build_opts* 
     return build_tables_subset_impl(g, opts, ngpus, virt, g->n, NULL, lat_q, quantum_ns, rel, NULL,
                                     NULL, stats);
 }
+
+/* ------------------------------------------------------------------------------------------ */
+/* Routes (routes.hip): the distance rows by the table build's own choice of algorithm, then   */
+/* the route pass over them -- never a builder's internal predecessors, so the pass stays a     */
+/* check on the builders.                                                                       */
+/* ------------------------------------------------------------------------------------------ */
+extern "C" int srt_routes_rows_device(const srt_sparse_graph* g, int32_t nsrc, const int32_t* srcs,
+                                      int32_t src_begin, const uint32_t* lat_rows, size_t ldl,
+                                      int32_t* pred, int32_t* first, int32_t* hops, size_t ldo,
+                                      void* stream, srt_route_stats* stats) {
+    if (!g || nsrc < 1 || !lat_rows || ldl < (size_t)g->n ||
+        (!srcs && (src_begin < 0 || (int64_t)src_begin + nsrc > g->n))) {
+        srt_set_error("srt_routes_rows_device: bad arguments");
+        return SRT_E_ARG;
+    }
+    if (g->wide) {
+        srt_set_error("srt_routes_rows_device: shortest-path latencies may pass the u32 range; the "
+                      "route pass reads u32 rows only");
+        return SRT_E_RANGE;
+    }
+    srt_route_stats local;
+    memset(&local, 0, sizeof(local));
+    const int rc = srt_routes_rows_timed(g->n, nsrc, srcs, src_begin, 0, lat_rows, ldl, g->irp,
+                                         g->icol, g->iw, pred, first, hops, ldo,
+                                         (hipStream_t)stream, &local);
+    if (!rc && stats) *stats = local;
+    return rc;
+}
+
+/* one GPU: rows of the sources verts (NULL: every vertex) into the host outputs, in chunks */
+static int routes_one(const srt_canon* c, const srt_build_opts* opts, int algo, int nsub,
+                      const int32_t* verts, int32_t* const hout[3], srt_route_stats* stats) {
+    const int n = c->n;
+    const int dev = opts ? opts->device : 0;
+    srt_route_stats local;
+    memset(&local, 0, sizeof(local));
+    srt_build_stats bs;
+    memset(&bs, 0, sizeof(bs));
+    dbufs B;
+    B.k = 0;
+    hipStream_t st = NULL;
+    int32_t* dverts = NULL;
+    int32_t* dout[3] = {NULL, NULL, NULL};
+    uint32_t *dw = NULL, *dlat = NULL, *iw = NULL;
+    double *dr = NULL, *drel = NULL;
+    int32_t *irp = NULL, *icol = NULL;
+    srt_sparse_graph* sg = NULL;
+    const int nout = (hout[0] ? 1 : 0) + (hout[1] ? 1 : 0) + (hout[2] ? 1 : 0);
+    const bool dense = algo == SRT_ALGO_DENSE_FW;
+    const int ld = srt_ceil_div(n, 128) * 128;
+    const size_t per_row = (size_t)n * ((dense ? 0 : 12) + 4 * (size_t)(nout ? nout : 1));
+    int chunk = nsub;
+    int rc = SRT_OK;
+    TRYHIP(hipSetDevice(dev));
+    TRYHIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    if (verts) {
+        TRY(dalloc(&B, (void**)&dverts, (size_t)nsub * sizeof(int32_t)));
+        TRYHIP(hipMemcpyAsync(dverts, verts, (size_t)nsub * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    }
+    if (dense) {
+        if (n > SRT_DENSE_MAX_N) {
+            srt_set_error("dense build supports n <= %d (n = %d); use the sparse SSSP",
+                          SRT_DENSE_MAX_N, n);
+            rc = SRT_E_RANGE;
+            goto out;
+        }
+        const size_t ll = (size_t)ld * ld;
+        TRY(dalloc(&B, (void**)&dw, ll * sizeof(uint32_t)));
+        TRY(dalloc(&B, (void**)&dr, ll * sizeof(double)));
+        TRY(dalloc(&B, (void**)&dlat, ll * sizeof(uint32_t)));
+        TRY(dalloc(&B, (void**)&drel, ll * sizeof(double)));
+        TRY(dense_upload(c, ld, 0, ld, dw, dr, st, 1));
+        TRY(srt_dense_build_device_ms(n, ld, c->directed, dw, dr, dlat, drel, NULL, c->quantum_ns, st,
+                                      opts ? opts->fw_block : 0, &bs));
+        local.ms_tables = bs.ms_total;
+        TRY(srt_routes_ess_build(n, ld, c->directed, dw, dlat, st, &irp, &icol, &iw, &local.ess_arcs,
+                                 &local.ms_routes));
+    } else {
+        TRY(sparse_graph_from_canon(c, dev, &sg));
+    }
+    {
+        const size_t cb = chunk_budget(0, 1) / per_row;
+        chunk = (int)(cb < (size_t)nsub ? (cb > 0 ? cb : 1) : (size_t)nsub);
+    }
+    if (!dense) {
+        TRY(dalloc(&B, (void**)&dlat, (size_t)chunk * n * sizeof(uint32_t)));
+        TRY(dalloc(&B, (void**)&drel, (size_t)chunk * n * sizeof(double)));
+    }
+    for (int i = 0; i < 3; i++)
+        if (hout[i]) TRY(dalloc(&B, (void**)&dout[i], (size_t)chunk * n * sizeof(int32_t)));
+    for (int r0 = 0; r0 < nsub; r0 += chunk) {
+        const int cnt = r0 + chunk < nsub ? chunk : nsub - r0;
+        const int32_t* cs = verts ? dverts + r0 : NULL;
+        if (dense) {
+            TRY(srt_routes_rows_timed(n, cnt, cs, r0, 1, dlat, (size_t)ld, irp, icol, iw, dout[0],
+                                      dout[1], dout[2], (size_t)n, st, &local));
+        } else {
+            memset(&bs, 0, sizeof(bs));
+            TRY(verts ? sparse_rows(sg, 0, cnt, cs, dlat, drel, NULL, st, &bs)
+                      : sparse_rows(sg, r0, r0 + cnt, NULL, dlat, drel, NULL, st, &bs));
+            local.ms_tables += bs.ms_total;
+            TRY(srt_routes_rows_timed(n, cnt, cs, r0, 0, dlat, (size_t)n, sg->irp, sg->icol, sg->iw,
+                                      dout[0], dout[1], dout[2], (size_t)n, st, &local));
+        }
+        const size_t w4 = (size_t)n * sizeof(int32_t);
+        for (int i = 0; i < 3; i++)
+            if (hout[i]) TRY(table_download(hout[i] + (size_t)r0 * n, w4, dout[i], w4, w4, cnt, st, 1));
+    }
+    if (stats) *stats = local;
+out:
+    if (st) {
+        srt_routes_ess_free(irp, icol, iw, st);
+        (void)hipStreamSynchronize(st);
+        (void)hipStreamDestroy(st);
+    }
+    srt_sparse_graph_free(sg);
+    dfree(&B);
+    return rc;
+}
+
+/* direct mode (topology.c:1816-1858): every pair is its own edge */
+static int routes_direct(const srt_edges* g, int32_t nsrc, const int32_t* srcs,
+                         int32_t* const hout[3]) {
+    const int64_t n = g->n;
+    if (n > SRT_DENSE_MAX_N) {
+        srt_set_error("dense build supports n <= %d (n = %d); use the sparse SSSP", SRT_DENSE_MAX_N,
+                      g->n);
+        return SRT_E_RANGE;
+    }
+    std::vector<uint8_t> have((size_t)((n * n + 7) / 8), 0);
+    int64_t pairs = 0;
+    auto mark = [&](int64_t u, int64_t v) {
+        const int64_t i = u * n + v;
+        if (!(have[(size_t)(i >> 3)] >> (i & 7) & 1)) {
+            have[(size_t)(i >> 3)] |= (uint8_t)(1u << (i & 7));
+            ++pairs;
+        }
+    };
+    for (int64_t e = 0; e < g->m; e++) {
+        const int32_t u = g->src[e], v = g->dst[e];
+        if (u < 0 || u >= n || v < 0 || v >= n) {
+            srt_set_error("srt_build_routes: edge %lld has a vertex outside [0, %d)", (long long)e, g->n);
+            return SRT_E_ARG;
+        }
+        mark(u, v);
+        if (!g->directed) mark(v, u);
+    }
+    if (pairs != n * n) {
+        srt_set_error("use_shortest_path=false requires a complete graph");
+        return SRT_E_INVALID;
+    }
+    for (int32_t i = 0; i < nsrc; i++) {
+        const int32_t s = srcs ? srcs[i] : i;
+        for (int32_t t = 0; t < n; t++) {
+            const size_t o = (size_t)i * n + t;
+            if (hout[0]) hout[0][o] = t == s ? -1 : s;
+            if (hout[1]) hout[1][o] = t == s ? -1 : t;
+            if (hout[2]) hout[2][o] = t == s ? 0 : 1;
+        }
+    }
+    return SRT_OK;
+}
+
+extern "C" int srt_build_routes(const srt_edges* g, const srt_build_opts* opts, int32_t nsrc,
+                                const int32_t* srcs, int32_t* pred, int32_t* first_hop,
+                                int32_t* hops, srt_route_stats* stats) {
+    if (!g || g->n <= 0) {
+        srt_set_error("srt_build_routes: null argument");
+        return SRT_E_ARG;
+    }
+    if (check_verts(g->n, nsrc, srcs)) {
+        srt_set_error("srt_build_routes: the sources must be 1..n strictly increasing vertex "
+                      "indices (or NULL with nsrc = n)");
+        return SRT_E_ARG;
+    }
+    int32_t* const hout[3] = {pred, first_hop, hops};
+    const int use_sp = opts ? opts->use_shortest_path : 1;
+    if (!use_sp) {
+        if (stats) memset(stats, 0, sizeof(*stats));
+        return routes_direct(g, nsrc, srcs, hout);
+    }
+    if (srt_device_count() < 1) {
+        srt_set_error("srt_build_routes: no HIP device");
+        return SRT_E_DEVICE;
+    }
+    /* the table build's own route to an algorithm (build_tables_subset_impl) */
+    const int forced = opts ? opts->algo : SRT_ALGO_AUTO;
+    int edge_form = 0;
+    if (forced != SRT_ALGO_SPARSE_SSSP && g->n <= SRT_DENSE_MAX_N && g->m > 0) {
+        const double n = g->n, ub = (double)g->m * (g->directed ? 1 : 2);
+        edge_form = g->n <= 2048 || ub * 16.0 >= n * n || forced == SRT_ALGO_DENSE_FW;
+    }
+    int rc = SRT_OK;
+    for (int attempt = 0; attempt < 2; attempt++) {
+        srt_canon c;
+        if (edge_form && attempt == 0 && canon_from_edges(g, &c) == 0) {
+            c.verify_dense = forced != SRT_ALGO_DENSE_FW;
+        } else {
+            if (attempt == 0) edge_form = 0;
+            rc = srt_canon_build(g, &c);
+            if (rc) return rc;
+        }
+        const int algo = c.wide && forced != SRT_ALGO_DENSE_FW ? SRT_ALGO_SPARSE_SSSP
+                                                                : choose_algo(&c, opts);
+        if (c.wide) {
+            srt_set_error("srt_build_routes: shortest-path latencies may pass the u32 range (bound "
+                          "%llu quanta of %llu ns); the route pass reads u32 rows only",
+                          (unsigned long long)c.dist_bound, (unsigned long long)c.quantum_ns);
+            srt_canon_free(&c);
+            return SRT_E_RANGE;
+        }
+        rc = routes_one(&c, opts, algo, nsrc, srcs, hout, stats);
+        srt_canon_free(&c);
+        if (rc != SRT_FALLBACK_CANON) break;
+    }
+    return rc;
+}

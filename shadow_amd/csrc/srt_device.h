@@ -268,6 +268,25 @@ int srt_tie_count_rows(int n, int nrows, const int32_t* srcs, int src_begin, con
                        int64_t* tied, hipStream_t st);
 int srt_quanta_to_ms(int rows, int cols, const uint32_t* w, size_t ldw, uint64_t q, double* out,
                      size_t ldo, hipStream_t st);
+/* routes.hip: predecessor / first hop / hop count rows from distance rows and an in-arc CSR (any
+ * output NULL). Row r is source srcs[r] (or src_begin + r), its distances row s (by_src) or row r
+ * of D. Returns after the stream; raises *max_hops, ors the staging forms taken into *forms */
+int srt_routes_rows(int n, int nrows, const int32_t* srcs, int src_begin, int by_src,
+                    const uint32_t* D, size_t ldd, const int32_t* irp, const int32_t* icol,
+                    const uint32_t* iw, int32_t* pred, int32_t* first, int32_t* hops, size_t ldo,
+                    hipStream_t st, int32_t* max_hops, int32_t* forms);
+/* the same between HIP events, added to *stats (ms_routes, max_hops, stage_forms) */
+int srt_routes_rows_timed(int n, int nrows, const int32_t* srcs, int src_begin, int by_src,
+                          const uint32_t* D, size_t ldd, const int32_t* irp, const int32_t* icol,
+                          const uint32_t* iw, int32_t* pred, int32_t* first, int32_t* hops,
+                          size_t ldo, hipStream_t st, srt_route_stats* stats);
+/* the essential in-arc CSR of a dense graph and its finished lat table (both ld x ld), from the
+ * scratch pool (*ms += the compaction's HIP-event time); srt_routes_ess_free returns it
+ * (stream-ordered) */
+int srt_routes_ess_build(int n, int ld, int directed, const uint32_t* w, const uint32_t* lat,
+                         hipStream_t st, int32_t** irp, int32_t** icol, uint32_t** iw,
+                         int64_t* arcs, double* ms);
+void srt_routes_ess_free(int32_t* irp, int32_t* icol, uint32_t* iw, hipStream_t st);
 /* collectives: all-gather of equal byte blocks, rank q's block at buf + q * bytes */
 int srt_coll_allgather(const srt_comm* c, void* buf, size_t bytes, hipStream_t st);
 

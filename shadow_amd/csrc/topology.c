@@ -330,7 +330,31 @@ struct _Topology {
     /* attach index (built on the first attach) */
     pthread_mutex_t ax_lock;
     void* ax;
+    /* routes (srt_topology_route*): one predecessor row (n int32) per source vertex asked for or
+     * attached, kept until topology_free. A miss builds under route_lock and publishes the rows
+     * with release stores; readers load them with acquire and never wait for a build they do not
+     * need. */
+    pthread_mutex_t route_lock;
+    _Atomic(int32_t*)* route_rows; /* n pointers, NULL until built */
+    struct route_batch* route_batches;
+    int route_failed;
+    atomic_int route_builds; /* srt_build_routes calls made */
+    _Atomic(struct arc_index*) arcs; /* (from, to) -> canonical edge, built on the first string */
 };
+
+/* the rows one srt_build_routes call produced */
+typedef struct route_batch {
+    int32_t* rows;
+    struct route_batch* next;
+} route_batch;
+
+/* the canonical arc of every ordered vertex pair (graph.c: the minimum latency, then the lowest
+ * edge index), sorted by key = from << 32 | to */
+typedef struct arc_index {
+    int64_t count;
+    uint64_t* key;
+    int64_t* edge;
+} arc_index;
 
 static int magic_ok(const Topology* t) { return t && t->magic == TOPOLOGY_MAGIC; }
 
@@ -676,6 +700,7 @@ static Topology* topology_from_text(const char* text, size_t len, int useShortes
     pthread_mutex_init(&t->build_lock, NULL);
     pthread_mutex_init(&t->ax_lock, NULL);
     pthread_mutex_init(&t->min_lock, NULL);
+    pthread_mutex_init(&t->route_lock, NULL);
     atomic_store(&t->tb, NULL);
     atomic_store(&t->attach_gen, 0);
     t->min_path_ms = 0.0;
@@ -695,7 +720,8 @@ static Topology* topology_from_text(const char* text, size_t len, int useShortes
         return NULL;
     }
     t->po = srt_pair_order_new(t->n, t->directed, t->use_shortest_path);
-    if (!t->po || cnt_init(&t->counters, t->n)) {
+    t->route_rows = (_Atomic(int32_t*)*)calloc((size_t)t->n, sizeof(*t->route_rows));
+    if (!t->po || !t->route_rows || cnt_init(&t->counters, t->n)) {
         srt_log(SRT_LOG_ERROR, "out of memory for the path order of %d vertices", t->n);
         topology_free(t);
         return NULL;
@@ -773,6 +799,20 @@ void topology_free(Topology* t) {
     srt_pair_order_free(t->po);
     pthread_mutex_destroy(&t->ax_lock);
     pthread_mutex_destroy(&t->min_lock);
+    pthread_mutex_destroy(&t->route_lock);
+    for (route_batch* b = t->route_batches; b;) {
+        route_batch* nx = b->next;
+        free(b->rows);
+        free(b);
+        b = nx;
+    }
+    free((void*)t->route_rows);
+    arc_index* ax = atomic_load(&t->arcs);
+    if (ax) {
+        free(ax->key);
+        free(ax->edge);
+        free(ax);
+    }
     t->magic = 0;
     free(t);
 }
@@ -1586,3 +1626,208 @@ int32_t srt_topology_vertex_count(Topology* t) { return magic_ok(t) ? t->n : -1;
 int64_t srt_topology_edge_count(Topology* t) { return magic_ok(t) ? t->m : -1; }
 int srt_topology_is_directed(Topology* t) { return magic_ok(t) ? t->directed : -1; }
 int srt_topology_is_complete(Topology* t) { return magic_ok(t) ? t->complete : -1; }
+
+/* ---- routes: which way a path goes ------------------------------------------------------- *
+ * The reference logs, for every path a source run stores, the vertices and edges it crosses
+ * (topology.c:1322, :1368-1369, :1770-1773). Here the route pass (routes.hip) recovers the
+ * canonical predecessors of a source's own row; the queries below walk them. They record no
+ * pair-order lookup, touch no packet counter or path count and offer nothing to the runahead
+ * hook. */
+static const int32_t* route_row(Topology* t, int32_t s) {
+    int32_t* row = atomic_load_explicit(&t->route_rows[s], memory_order_acquire);
+    if (row) return row;
+    const int32_t n = t->n;
+    pthread_mutex_lock(&t->route_lock);
+    row = atomic_load_explicit(&t->route_rows[s], memory_order_acquire);
+    if (!row && !t->route_failed) {
+        /* the asked source plus every attached vertex without a row, within 1 GiB of rows */
+        int32_t* list = (int32_t*)malloc((size_t)n * sizeof(int32_t));
+        int32_t k = 0;
+        if (list) {
+            pthread_rwlock_rdlock(&t->ip_lock);
+            for (int32_t v = 0; v < n; v++)
+                if (v == s || (t->attached[v] && !atomic_load_explicit(&t->route_rows[v], memory_order_relaxed)))
+                    list[k++] = v;
+            pthread_rwlock_unlock(&t->ip_lock);
+            if ((size_t)k * (size_t)n * sizeof(int32_t) > ((size_t)1 << 30)) {
+                list[0] = s;
+                k = 1;
+            }
+        }
+        route_batch* b = (route_batch*)calloc(1, sizeof(route_batch));
+        if (b) b->rows = (int32_t*)malloc((size_t)(k ? k : 1) * (size_t)n * sizeof(int32_t));
+        int rc = list && b && b->rows ? SRT_OK : SRT_E_NOMEM;
+        if (!rc) {
+            srt_edges e;
+            srt_topology_edges(t, &e);
+            srt_build_opts o = t->opts;
+            o.use_shortest_path = t->use_shortest_path;
+            srt_route_stats rs;
+            rc = srt_build_routes(&e, &o, k, k == n ? NULL : list, b->rows, NULL, NULL, &rs);
+            atomic_fetch_add(&t->route_builds, 1);
+        } else {
+            srt_set_error("out of memory for %d route rows", k);
+        }
+        if (rc) {
+            t->route_failed = 1;
+            srt_log(SRT_LOG_ERROR, "route build failed (%d): %s", rc, srt_last_error());
+            if (b) free(b->rows);
+            free(b);
+        } else {
+            b->next = t->route_batches;
+            t->route_batches = b;
+            for (int32_t i = 0; i < k; i++)
+                atomic_store_explicit(&t->route_rows[list[i]], b->rows + (size_t)i * n,
+                                      memory_order_release);
+            row = atomic_load_explicit(&t->route_rows[s], memory_order_acquire);
+            srt_log(SRT_LOG_INFO, "routes built for %d source vertices", k);
+        }
+        free(list);
+    }
+    pthread_mutex_unlock(&t->route_lock);
+    return row;
+}
+
+int32_t srt_topology_route_builds(Topology* t) {
+    return magic_ok(t) ? atomic_load(&t->route_builds) : -1;
+}
+
+int32_t srt_topology_route(Topology* t, int32_t s, int32_t d, int32_t* verts, int32_t cap) {
+    if (!magic_ok(t) || s < 0 || s >= t->n || d < 0 || d >= t->n || cap < 0 || (cap > 0 && !verts))
+        return SRT_E_ARG;
+    if (s == d) {
+        if (cap > 0) verts[0] = s;
+        return 1;
+    }
+    const int32_t* row = route_row(t, s);
+    if (!row) return SRT_E_DEVICE;
+    if (row[d] < 0) return SRT_E_NOPATH;
+    int32_t count = 1;
+    for (int32_t v = d; v != s; v = row[v]) {
+        if (row[v] < 0 || count > t->n) return SRT_E_NOPATH; /* a broken chain: never a loop */
+        ++count;
+    }
+    int32_t i = count - 1;
+    for (int32_t v = d; i >= 0; v = row[v], --i) {
+        if (i < cap) verts[i] = v;
+        if (v == s) break;
+    }
+    return count;
+}
+
+int32_t srt_topology_route_ip(Topology* t, uint32_t srcIp, uint32_t dstIp, int32_t* verts,
+                              int32_t cap) {
+    if (!magic_ok(t)) return SRT_E_ARG;
+    const int32_t s = srt_topology_vertex_of_ip(t, srcIp), d = srt_topology_vertex_of_ip(t, dstIp);
+    if (s < 0 || d < 0) return SRT_E_UNATTACHED;
+    return srt_topology_route(t, s, d, verts, cap);
+}
+
+typedef struct {
+    uint64_t key;
+    int64_t lat;
+    int64_t edge;
+} arc_ent;
+
+static int arc_ent_cmp(const void* a, const void* b) {
+    const arc_ent *x = (const arc_ent*)a, *y = (const arc_ent*)b;
+    if (x->key != y->key) return x->key < y->key ? -1 : 1;
+    if (x->lat != y->lat) return x->lat < y->lat ? -1 : 1;
+    return x->edge < y->edge ? -1 : x->edge > y->edge;
+}
+
+static const arc_index* arc_index_of(Topology* t) {
+    arc_index* ax = atomic_load_explicit(&t->arcs, memory_order_acquire);
+    if (ax) return ax;
+    pthread_mutex_lock(&t->route_lock);
+    ax = atomic_load_explicit(&t->arcs, memory_order_acquire);
+    if (!ax) {
+        const int64_t cap = t->m * (t->directed ? 1 : 2);
+        arc_ent* ents = (arc_ent*)malloc((size_t)(cap ? cap : 1) * sizeof(arc_ent));
+        ax = (arc_index*)calloc(1, sizeof(arc_index));
+        int64_t k = 0;
+        if (ents && ax) {
+            for (int64_t e = 0; e < t->m; e++) {
+                const uint64_t u = (uint32_t)t->esrc[e], v = (uint32_t)t->edst[e];
+                ents[k++] = (arc_ent){(u << 32) | v, t->elat_ns[e], e};
+                if (!t->directed && u != v) ents[k++] = (arc_ent){(v << 32) | u, t->elat_ns[e], e};
+            }
+            qsort(ents, (size_t)k, sizeof(arc_ent), arc_ent_cmp);
+            ax->key = (uint64_t*)malloc((size_t)(k ? k : 1) * sizeof(uint64_t));
+            ax->edge = (int64_t*)malloc((size_t)(k ? k : 1) * sizeof(int64_t));
+        }
+        if (!ents || !ax || !ax->key || !ax->edge) {
+            if (ax) {
+                free(ax->key);
+                free(ax->edge);
+            }
+            free(ax);
+            ax = NULL;
+        } else {
+            for (int64_t i = 0; i < k; i++)
+                if (i == 0 || ents[i].key != ents[i - 1].key) {
+                    ax->key[ax->count] = ents[i].key;
+                    ax->edge[ax->count++] = ents[i].edge;
+                }
+            atomic_store_explicit(&t->arcs, ax, memory_order_release);
+        }
+        free(ents);
+    }
+    pthread_mutex_unlock(&t->route_lock);
+    return ax;
+}
+
+static int64_t arc_edge(const arc_index* ax, int32_t from, int32_t to) {
+    const uint64_t key = ((uint64_t)(uint32_t)from << 32) | (uint32_t)to;
+    int64_t lo = 0, hi = ax->count;
+    while (lo < hi) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (ax->key[mid] < key) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < ax->count && ax->key[lo] == key ? ax->edge[lo] : -1;
+}
+
+int64_t srt_topology_route_string_ip(Topology* t, uint32_t srcIp, uint32_t dstIp, char* buf,
+                                     size_t cap) {
+    if (!magic_ok(t) || (cap > 0 && !buf)) return SRT_E_ARG;
+    const int32_t count = srt_topology_route_ip(t, srcIp, dstIp, NULL, 0);
+    if (count < 0) return count;
+    int32_t* verts = (int32_t*)malloc((size_t)count * sizeof(int32_t));
+    const arc_index* ax = count > 1 ? arc_index_of(t) : NULL;
+    if (!verts || (count > 1 && !ax)) {
+        free(verts);
+        return SRT_E_NOMEM;
+    }
+    srt_topology_route_ip(t, srcIp, dstIp, verts, count);
+    int64_t len = 0;
+    char piece[160];
+    if (cap > 0) buf[0] = 0;
+#define ROUTE_PUT()                                                              \
+    do {                                                                         \
+        const size_t pl = strlen(piece);                                         \
+        if ((size_t)len + 1 < cap) {                                             \
+            const size_t room = cap - 1 - (size_t)len, cp = pl < room ? pl : room; \
+            memcpy(buf + len, piece, cp);                                        \
+            buf[(size_t)len + cp] = 0;                                           \
+        }                                                                        \
+        len += (int64_t)pl;                                                      \
+    } while (0)
+    snprintf(piece, sizeof(piece), "%li", (long)t->vid[verts[0]]);
+    ROUTE_PUT();
+    for (int32_t i = 1; i < count; i++) {
+        const int64_t e = arc_edge(ax, verts[i - 1], verts[i]);
+        if (e < 0) { /* a predecessor without its arc: the rows and the graph disagree */
+            free(verts);
+            return SRT_E_NOPATH;
+        }
+        const double edgeLatency = (double)t->elat_ns[e] / 1e6;    /* topology.c:294 */
+        const double edgeReliability = 1.0f - t->eloss[e];         /* topology.c:396 */
+        snprintf(piece, sizeof(piece), "%s[%f,%f]-->%li", t->directed ? "--" : "<--", edgeLatency,
+                 1.0f - edgeReliability, (long)t->vid[verts[i]]);
+        ROUTE_PUT();
+    }
+#undef ROUTE_PUT
+    free(verts);
+    return len;
+}

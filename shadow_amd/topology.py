@@ -23,7 +23,7 @@ import struct
 import numpy as np
 
 from . import _lib
-from ._lib import BuildOpts, BuildStats, Edges, check, lib
+from ._lib import BuildOpts, BuildStats, Edges, RouteStats, check, lib
 
 
 def ip_to_net(ip) -> int:
@@ -242,6 +242,48 @@ class Topology:
     def min_latency_ms(self) -> float:
         return lib().srt_topology_min_latency_ms(self._h)
 
+    # -- routes --------------------------------------------------------------------------------
+    def route(self, src, dst, cap=None):
+        """srt_topology_route_ip: the vertex indices of the canonical path of src's own row, from
+        src's vertex to dst's (cap: at most that many of them; the full count is in
+        route_count)."""
+        s, d = ip_to_net(src), ip_to_net(dst)
+        k = lib().srt_topology_route_ip(self._h, s, d, None, 0)
+        if k < 0:
+            check(k, "srt_topology_route_ip")
+        self.route_count = k
+        m = k if cap is None else min(int(cap), k)
+        out = np.empty(max(m, 1), np.int32)
+        k = lib().srt_topology_route_ip(self._h, s, d, out.ctypes.data, m)
+        if k < 0:
+            check(k, "srt_topology_route_ip")
+        return out[:m].tolist()
+
+    def route_vertices(self, s: int, t: int):
+        """srt_topology_route between vertex indices (attached or not)."""
+        k = lib().srt_topology_route(self._h, int(s), int(t), None, 0)
+        if k < 0:
+            check(k, "srt_topology_route")
+        out = np.empty(k, np.int32)
+        check(min(lib().srt_topology_route(self._h, int(s), int(t), out.ctypes.data, k), 0),
+              "srt_topology_route")
+        return out.tolist()
+
+    def route_string(self, src, dst) -> str:
+        """The reference's `path:` log field for route(src, dst) (topology.c:1322, :1368-1369)."""
+        s, d = ip_to_net(src), ip_to_net(dst)
+        k = lib().srt_topology_route_string_ip(self._h, s, d, None, 0)
+        if k < 0:
+            check(k, "srt_topology_route_string_ip")
+        buf = ctypes.create_string_buffer(k + 1)
+        k = lib().srt_topology_route_string_ip(self._h, s, d, buf, k + 1)
+        if k < 0:
+            check(k, "srt_topology_route_string_ip")
+        return buf.value.decode()
+
+    def route_builds(self) -> int:
+        return lib().srt_topology_route_builds(self._h)
+
 
 MIN_HOOK = ctypes.CFUNCTYPE(None, ctypes.c_double)
 
@@ -315,6 +357,30 @@ def build_tables(n, directed, src, dst, lat_ns, loss, use_shortest_path=True, de
     return lat.astype(np.uint64) * np.uint64(q.value), rel, st
 
 
+def build_routes(n, directed, src, dst, lat_ns, loss, sources=None, use_shortest_path=True,
+                 device=0, algo=_lib.ALGO_AUTO):
+    """srt_build_routes on host arrays -> (pred, first_hop, hops int32 [k, n], stats) for the
+    sources `sources` (strictly increasing; None = every vertex)."""
+    src = np.ascontiguousarray(src, np.int32)
+    dst = np.ascontiguousarray(dst, np.int32)
+    lat_ns = np.ascontiguousarray(lat_ns, np.int64)
+    loss = np.ascontiguousarray(loss, np.float64)
+    e = Edges(n, int(bool(directed)), len(src), src.ctypes.data, dst.ctypes.data,
+              lat_ns.ctypes.data, loss.ctypes.data)
+    o = BuildOpts(device, algo, int(bool(use_shortest_path)), 0)
+    ss = None if sources is None else np.ascontiguousarray(sources, np.int32)
+    k = n if ss is None else len(ss)
+    pred = np.empty((k, n), np.int32)
+    first = np.empty((k, n), np.int32)
+    hops = np.empty((k, n), np.int32)
+    st = RouteStats()
+    check(lib().srt_build_routes(ctypes.byref(e), ctypes.byref(o), k,
+                                 None if ss is None else ss.ctypes.data, pred.ctypes.data,
+                                 first.ctypes.data, hops.ctypes.data, ctypes.byref(st)),
+          "srt_build_routes")
+    return pred, first, hops, st
+
+
 class SparseGraph:
     """Device-resident canonical CSR (srt_sparse_graph_*): rows of any source range are computed
     on the device into caller-provided device buffers (torch tensors or raw pointers)."""
@@ -350,6 +416,21 @@ class SparseGraph:
                                                ctypes.c_void_p(lat_ptr), ctypes.c_void_p(rel_ptr),
                                                None, ctypes.c_void_p(stream), st),
               "srt_sparse_graph_rows_list")
+
+    def routes_rows(self, lat_ptr, nsrc, pred_ptr=None, first_ptr=None, hops_ptr=None,
+                    srcs_ptr=None, src_begin=0, ldl=None, ldo=None, stream=None, stats=None):
+        """srt_routes_rows_device over device pointers: row i of lat (stride ldl, default n) and of
+        the int32 outputs (stride ldo, default n; any may be None) belongs to srcs[i], or
+        src_begin + i without a source list."""
+        st = ctypes.byref(stats) if stats is not None else None
+        check(lib().srt_routes_rows_device(self._h, int(nsrc), ctypes.c_void_p(srcs_ptr),
+                                           int(src_begin), ctypes.c_void_p(lat_ptr),
+                                           self.n if ldl is None else int(ldl),
+                                           ctypes.c_void_p(pred_ptr), ctypes.c_void_p(first_ptr),
+                                           ctypes.c_void_p(hops_ptr),
+                                           self.n if ldo is None else int(ldo),
+                                           ctypes.c_void_p(stream), st),
+              "srt_routes_rows_device")
 
     def free(self):
         if getattr(self, "_h", None):
