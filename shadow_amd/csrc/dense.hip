@@ -2232,8 +2232,11 @@ static int dense_post_levels(int32_t n, int32_t ld, int32_t row0, int32_t nrows,
         SRT_HIPCHK(hipMemsetAsync(rel + (size_t)lrows * ld, 0, (size_t)(nrows - lrows) * ld * sizeof(double), st));
     }
     if (lrows > 0 && srt_levels_pkw_ready()) {
-        /* target-major packed words with the level (lvl_pred_kernel), one u32 transpose, then
-         * rel_pk_kernel, which writes the u32 rows too: no u8 rows, no f64 slab */
+        /* the packed words with the level, source-major rows of stride ld in ws->dt, then
+         * rel_pk_kernel, which writes the u32 rows too: no u8 rows, no f64 slab. The words come
+         * straight from lvl_pred_rows_kernel (no predt slab, no transpose); with the tie count,
+         * or under SRT_FORM pkw=2, target-major from lvl_pred_kernel and through one u32
+         * transpose */
         const size_t slab = (size_t)ld * nrows;
         size_t c1 = ws->dt_cap;
         if ((rc = ws_grow((void**)&ws->dt, &c1, slab, sizeof(uint32_t)))) return rc;
@@ -2248,17 +2251,22 @@ static int dense_post_levels(int32_t n, int32_t ld, int32_t row0, int32_t nrows,
         if (stats) stats->rel_table = ntab;
         uint32_t* pk = reinterpret_cast<uint32_t*>(ws->dt);
         if (kt) SRT_HIPCHK(hipEventRecord(ws->kev[0], st));
-        {   /* target-major packed words (with the level), then one u32 transpose */
+        const bool rows = !ties && srt_levels_pkw_ready() == 1;
+        SRT_HIPCHK(hipMemsetAsync(ws->depth + 1, 0, sizeof(int32_t), st));
+        if (rows) {
+            if ((rc = srt_levels_pred(pk, 3, nullptr, (size_t)ld, NULL, ws->depth + 1, &ws->pn_cap, st)))
+                return rc;
+        } else { /* target-major packed words (with the level), then one u32 transpose */
             size_t c2 = ws->predt_cap;
             if ((rc = ws_grow((void**)&ws->predt, &c2, slab, sizeof(int32_t)))) return rc;
             ws->predt_cap = c2;
-            SRT_HIPCHK(hipMemsetAsync(ws->depth + 1, 0, sizeof(int32_t), st));
             if ((rc = srt_levels_pred(ws->predt, 2, nullptr, (size_t)nrows, ties ? ws->ties : NULL,
                                       ws->depth + 1, &ws->pn_cap, st)))
                 return rc;
         }
         if (kt) SRT_HIPCHK(hipEventRecord(ws->kev[1], st));
-        transpose_kernel<uint32_t><<<dim3(srt_ceil_div(nrows, 64), srt_ceil_div(n, 64)), 256, 0, st>>>(
+        if (!rows)
+            transpose_kernel<uint32_t><<<dim3(srt_ceil_div(nrows, 64), srt_ceil_div(n, 64)), 256, 0, st>>>(
                 n, nrows, reinterpret_cast<const uint32_t*>(ws->predt), (size_t)nrows, pk, (size_t)ld);
         ws->pred16 = 2; /* dense_path_ms reads the packed words' low half */
         SRT_HIPCHK(hipMemsetAsync(ws->depth, 0, sizeof(int32_t), st));
@@ -2703,6 +2711,10 @@ static int dense_path_ms(int32_t n, int32_t ld, int32_t row0, int32_t nrows, con
     const int32_t* pred = reinterpret_cast<const int32_t*>(ws->dt);
     if (ws->pred16) { /* the level post pass left int16 rows: widened into the free slab */
         const size_t cnt = (size_t)lrows * ld;
+        /* (the source-major packed post pass keeps no predt slab: taken here, when asked for) */
+        size_t c2 = ws->predt_cap;
+        if ((rc = ws_grow((void**)&ws->predt, &c2, (size_t)nrows * ld, sizeof(int32_t)))) return rc;
+        ws->predt_cap = c2;
         const int64_t nb = srt_ceil_div((int64_t)cnt, 256);
         const unsigned g = (unsigned)(nb < 65536 ? nb : 65536);
         if (ws->pred16 == 2)

@@ -1821,6 +1821,230 @@ __global__ __launch_bounds__(256, 7) void lvl_pred_kernel(int n, int nw, int nch
                           rix, lev, predT, rT, ldp, ties, bkt, bcnt, cap);
 }
 
+/* The packed words source-major, no transpose (the packed form without the tie count): narrow
+ * units. A wave covers 4 targets x 16 words (512 sources), 16 lanes per target: lane (g, l) owns
+ * word c16 * 16 + l of target 32 * tg + 4 * wave + g. A workgroup's eight waves hold 32
+ * consecutive targets of one 512-source sub-chunk, so after the walk each source has a full
+ * 128-B run of its row (32 targets x 4 B) in the workgroup: the walk's sidx entries are the
+ * staging tile, and the output stage stores whole lines of pk[source][target] (row stride ld).
+ * The gathered slices are 64 B, and a pass over all targets touches n x 64 B per plane (2 MB on
+ * C4) where the 2,048-source units touch 8 MB; the walk itself is slower than the wide one (C4:
+ * 5.3-5.5 against 4.1 ms, L2 hit rate 0.40 against 0.51: four times the units re-read the arc
+ * offsets and the buckets) by less than the 1.65-ms transpose it removes. The rule, the words
+ * and the walk's order are lvl_pred_unit's; what differs:
+ *  - the in-arc group bounds and the walk's position are per 16-lane group; a group past its
+ *    bound or without a pending source has its gathers predicated off; the wave leaves a weight
+ *    when every group has, and a level when no lane has a pending source;
+ *  - a group's next LVL_PB arc offsets come with one vector load (lane l takes arc l of its
+ *    group) and reach the lanes by a cross-lane read inside the group (ds_bpermute), so no
+ *    register is held per in-flight gather for them;
+ *  - the direct arcs (w == d): lane l tests arc i0 + l of its group against the pending word of
+ *    the lane that owns the arc's source (one ds_bpermute) and writes that lane's sidx entry and
+ *    claimed bit through LDS;
+ *  - lvl_pred_near_kernel's buckets stay keyed by (target, 2,048-source chunk): a group reads
+ *    the bucket of its enclosing chunk and keeps the entries of its 512 sources.
+ * LDS per lane, LVL_RW_LANE = 24 words: 16 of sidx (32 u16), the claimed word (after the walk
+ * the five level planes, words 16..20), and three spare words that hold the target's group
+ * bounds (off[t][l], [16 + l], [32 + l]: weight w's bound is in lane w & 15, word 21 + (w >> 4)).
+ * A target's 16 lanes and 4 words of padding are LVL_RW_TGT = 388 words; 32 targets are 49,664 B,
+ * three workgroups of 512 threads per CU (six waves per SIMD). */
+#define LVL_RW_LANE 24
+#define LVL_RW_TGT (16 * LVL_RW_LANE + 4)
+__global__ __launch_bounds__(512, 6) void lvl_pred_rows_kernel(int n, int nw, int nchunk, int src0, int nsrc,
+                                                                int nlev, unsigned ntg, unsigned nunit,
+                                                                const int32_t* __restrict__ off,
+                                                                const uint32_t* __restrict__ arcs,
+                                                                const uint32_t* __restrict__ aoff,
+                                                                const uint16_t* __restrict__ rix,
+                                                                const uint32_t* __restrict__ lev,
+                                                                uint32_t* __restrict__ pk, size_t ld,
+                                                                const uint32_t* __restrict__ bkt,
+                                                                const uint32_t* __restrict__ bcnt, int cap) {
+    __shared__ __attribute__((aligned(16))) uint32_t sw[32 * LVL_RW_TGT];
+    const int lane = threadIdx.x & 63, l = lane & 15;
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int gl = wv * 4 + (lane >> 4); /* the lane's target inside the workgroup's 32 */
+    uint32_t* tgt = sw + gl * LVL_RW_TGT;
+    uint32_t* mine = tgt + l * LVL_RW_LANE;
+    uint16_t* my = reinterpret_cast<uint16_t*>(mine);
+    const size_t plane = (size_t)n * nw;
+    auto wave_sync = [] {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    };
+    /* p anywhere in the lane's 16-lane group (every lane of the wave calls it) */
+    auto gany = [&](bool p) -> bool {
+        return ((__ballot(p) >> (lane & 48)) & 0xFFFFull) != 0ull;
+    };
+    /* chunk-major, consecutive workgroups (one per XCD in turn) on consecutive target groups:
+     * the whole GPU gathers from one sub-chunk's slices at a time */
+    for (unsigned u = blockIdx.x; u < nunit; u += gridDim.x) {
+        const int c16 = (int)(u / ntg), tg = (int)(u % ntg);
+        const int t = tg * 32 + gl, word = c16 * 16 + l;
+        const bool tv = t < n, act = tv && word < nw;
+        const int cs0 = c16 * 512; /* the sub-chunk's first local source */
+#pragma unroll
+        for (int q = 0; q < 16; q += 4)
+            *reinterpret_cast<uint4*>(mine + q) = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
+        mine[16] = 0u;
+        {
+            const int32_t* ot = off + (size_t)(tv ? t : 0) * LVL_STRIDE;
+            mine[21] = tv ? (uint32_t)ot[l] : 0u;
+            mine[22] = tv ? (uint32_t)ot[16 + l] : 0u;
+            mine[23] = tv ? (uint32_t)ot[32 + l] : 0u;
+        }
+        wave_sync();
+        auto otl = [&](int w) -> int { return (int)tgt[(w & 15) * LVL_RW_LANE + 21 + (w >> 4)]; };
+        const int a_t = otl(0);
+        const uint32_t lane4 = (uint32_t)(act ? word : 0) * 4u;
+        /* the bucket of (t, enclosing chunk): the entries of this sub-chunk's sources into
+         * their owners' sidx slots and claimed words. An overflowed bucket is ignored. */
+        bool pn = false;
+        if (bkt) {
+            const size_t un = (size_t)(tv ? t : 0) * nchunk + (c16 >> 2);
+            const int k = tv ? (int)bcnt[un] : cap + 1;
+            pn = k <= cap;
+            const uint32_t* ub = bkt + un * cap;
+            for (int i = l; pn && i < k; i += 16) {
+                const uint32_t e = ub[i], sl = e & 2047u;
+                if ((int)(sl >> 9) != (c16 & 3)) continue;
+                uint32_t* o = tgt + ((sl >> 5) & 15u) * LVL_RW_LANE;
+                reinterpret_cast<uint16_t*>(o)[sl & 31u] = (uint16_t)(e >> 11);
+                atomicOr(&o[16], 1u << (sl & 31u));
+            }
+            wave_sync();
+        }
+        uint32_t lvb[5] = {0u, 0u, 0u, 0u, 0u};
+        for (int d = 1; d <= nlev; ++d) {
+            uint32_t pend = act ? lev[(size_t)(d - 1) * plane + (size_t)t * nw + word] : 0u;
+#pragma unroll
+            for (int k = 0; k < 5; ++k)
+                if ((d >> k) & 1) lvb[k] |= pend;
+            pend &= ~mine[16];
+            if (!__any(pend != 0u)) continue;
+            for (int w = d; w >= 1; --w) {
+                const bool gp = gany(pend != 0u);
+                const int g0 = otl(w);
+                int g1 = otl(w + 1);
+                if (!gp || (pn && w == d - 1)) g1 = g0; /* nothing pending, or the pre-pass took this group */
+                if (!__any(g0 < g1)) continue;
+                if (w == d) {
+                    /* the direct arc (u, t): tight for the source u itself; distinct arcs have
+                     * distinct sources, so the order does not matter */
+                    for (int i0 = g0; __any(i0 < g1); i0 += 16) {
+                        const int i = i0 + l;
+                        const int us = i < g1 ? (int)(arcs[i] & 0xFFFFu) - src0 : -1;
+                        const bool in = us >= 0 && us < nsrc && (unsigned)(us - cs0) < 512u;
+                        const int ow = in ? (us >> 5) & 15 : 0;
+                        const uint32_t op = (uint32_t)__shfl((int)pend, ow, 16);
+                        if (in && ((op >> (us & 31)) & 1u)) {
+                            uint32_t* o = tgt + ow * LVL_RW_LANE;
+                            reinterpret_cast<uint16_t*>(o)[us & 31] = (uint16_t)(i - a_t);
+                            atomicOr(&o[16], 1u << (us & 31));
+                        }
+                    }
+                    wave_sync();
+                    pend &= ~mine[16];
+                } else {
+                    /* LVL_PB gathers per batch, software-pipelined as lvl_pred_unit's; e is the
+                     * group's end of the walk, pulled in once none of its sources is pending */
+                    const char* base = reinterpret_cast<const char*>(lev + (size_t)(d - w - 1) * plane);
+                    int i = g0, e = g1;
+                    uint32_t v[LVL_PB], vn[LVL_PB];
+                    {
+                        const uint32_t aq = l < LVL_PB && i + l < e ? aoff[i + l] : 0u;
+#pragma unroll
+                        for (int q = 0; q < LVL_PB; ++q) {
+                            const uint32_t a = (uint32_t)__shfl((int)aq, q, 16);
+                            v[q] = i + q < e ? *reinterpret_cast<const uint32_t*>(base + (a + lane4)) : 0u;
+                        }
+                    }
+                    while (__any(i < e)) {
+                        const int i2 = i + LVL_PB;
+                        {
+                            const uint32_t aq = l < LVL_PB && i2 + l < e ? aoff[i2 + l] : 0u;
+#pragma unroll
+                            for (int q = 0; q < LVL_PB; ++q) {
+                                const uint32_t a = (uint32_t)__shfl((int)aq, q, 16);
+                                vn[q] = i2 + q < e ? *reinterpret_cast<const uint32_t*>(base + (a + lane4)) : 0u;
+                            }
+                        }
+#pragma unroll
+                        for (int q = 0; q < LVL_PB; ++q) { /* a source takes its first tight arc */
+                            uint32_t nb = v[q] & pend;
+                            pend &= ~nb;
+                            while (nb) {
+                                my[__builtin_ctz(nb)] = (uint16_t)(i + q - a_t);
+                                nb &= nb - 1u;
+                            }
+                        }
+#pragma unroll
+                        for (int q = 0; q < LVL_PB; ++q) v[q] = vn[q];
+                        i = i2;
+                        if (!gany(pend != 0u)) e = min(e, i);
+                    }
+                }
+                if (!__any(pend != 0u)) break;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 5; ++k) mine[16 + k] = lvb[k];
+        __syncthreads();
+        /* Output: thread (wave, k = lane / 8, tq = lane % 8) takes 8 consecutive sources -- bits
+         * oct * 8.. of word wd = 2 * wave + k / 4, oct = k % 4 -- of targets 4 * tq .. + 3: one
+         * 16-B piece per source, the eight tq lanes one source's 128-B run, so every store
+         * instruction writes eight whole lines. nsrc is a multiple of 128: whole groups of 8. */
+        {
+            const int tq = lane & 7, kq = lane >> 3;
+            const int wd = 2 * wv + (kq >> 2), oct = kq & 3;
+            const int sl0 = cs0 + wd * 32 + oct * 8, t0 = tg * 32 + 4 * tq;
+            if (sl0 < nsrc && t0 < n) {
+                uint32_t sx[4][4], lq[4][5];
+                int at[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const uint32_t* p = sw + (4 * tq + j) * LVL_RW_TGT;
+                    at[j] = (int)p[21];
+                    p += wd * LVL_RW_LANE;
+                    const uint4 a = *reinterpret_cast<const uint4*>(p + oct * 4);
+                    const uint4 b = *reinterpret_cast<const uint4*>(p + 16);
+                    sx[j][0] = a.x, sx[j][1] = a.y, sx[j][2] = a.z, sx[j][3] = a.w;
+                    lq[j][0] = b.x >> (oct * 8), lq[j][1] = b.y >> (oct * 8);
+                    lq[j][2] = b.z >> (oct * 8), lq[j][3] = b.w >> (oct * 8);
+                    lq[j][4] = p[20] >> (oct * 8);
+                }
+#pragma unroll 1 /* (unrolled twice: 80 VGPRs and 32 B of scratch, 6.15 against 5.98 ms) */
+                for (int e = 0; e < 8; ++e) {
+                    const int sg = src0 + sl0 + e;
+                    uint32_t kv[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const uint32_t x = (sx[j][e >> 1] >> (16 * (e & 1))) & 0xFFFFu;
+                        const bool h = sg < n && sg != t0 + j && t0 + j < n && x != 0xFFFFu;
+                        const int k = at[j] + (h ? (int)x : 0);
+                        uint32_t lv = 0;
+#pragma unroll
+                        for (int kk = 0; kk < 5; ++kk) lv |= ((lq[j][kk] >> e) & 1u) << kk;
+                        kv[j] = h ? ((arcs[k] & 0xFFFFu) | (uint32_t)rix[k] << 16 | lv << 27) : 0xFFFFu;
+                    }
+                    uint32_t* pp = pk + (size_t)(sl0 + e) * ld + t0;
+                    if (t0 + 3 < n) { /* non-temporal, as lvl_pred_unit's words */
+                        typedef unsigned u32x4n __attribute__((ext_vector_type(4)));
+                        __builtin_nontemporal_store((u32x4n){kv[0], kv[1], kv[2], kv[3]},
+                                                    reinterpret_cast<u32x4n*>(pp));
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j)
+                            if (t0 + j < n) pp[j] = kv[j];
+                    }
+                }
+            }
+        }
+        __syncthreads(); /* the next unit's walk rewrites the tile */
+    }
+}
+
 __global__ void lvl_sum_kernel(const unsigned long long* __restrict__ v, int k,
                                unsigned long long* __restrict__ out) {
     unsigned long long s = 0;
@@ -1888,14 +2112,14 @@ static int lvl_pn_cap(const unsigned long long* hist, int n, int nsrc, int D) {
     return (double)cap < need ? 4096 : cap; /* (4096: more than a bucket can ever hold) */
 }
 
-/* persistent grid of a 256-thread unit kernel: its resident workgroups per CU x the CUs, a multiple
- * of 8 (one share per XCD), at most the unit blocks */
-static unsigned lvl_grid(const void* fn, unsigned nblk, int reserve_cus = 0) {
+/* persistent grid of a unit kernel (workgroups of `threads`): its resident workgroups per CU x the
+ * CUs, a multiple of 8 (one share per XCD), at most the unit blocks */
+static unsigned lvl_grid(const void* fn, unsigned nblk, int reserve_cus = 0, int threads = 256) {
     int dev = 0, cus = 256, per = 4;
     if (hipGetDevice(&dev) == hipSuccess)
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     cus = max(8, cus - reserve_cus);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, fn, 256, 0) != hipSuccess || per < 1) per = 4;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, fn, threads, 0) != hipSuccess || per < 1) per = 4;
     (void)hipGetLastError();
     unsigned g = (unsigned)(cus * per) & ~7u;
     if (g < 8) g = 8;
@@ -2896,10 +3120,12 @@ int srt_levels_build(const srt_comm* comm, int n, int ld, int row0, int nrows, i
         rix = NULL, rtab = NULL; /* (freed with the state) */
     /* the packed post pass writes the u32 rows itself (rel_pk_kernel): the table of distinct arc
      * reliabilities, 5-bit levels and u16 vertices (n <= 32768) */
-    /* 1: lvl_pred_kernel's target-major packed words with the level, one transpose, then
-     * rel_pk_kernel, which writes the u32 rows too; 0 (past the packed form, or SRT_FORM pkw=0):
-     * lvl_out8 rows + the predecessor rows + rel_tree_kernel */
-    const int pkw = rix && D <= 31 && n <= 32768 ? (srt_form_int("pkw", 1) != 0) : 0;
+    /* 1: the packed words with the level, source-major from lvl_pred_rows_kernel (with the tie
+     * count: as 2), then rel_pk_kernel, which writes the u32 rows too; 2 (SRT_FORM pkw=2):
+     * lvl_pred_kernel's target-major words and one transpose before rel_pk_kernel; 0 (past the
+     * packed form, or SRT_FORM pkw=0): lvl_out8 rows + the predecessor rows + rel_tree_kernel */
+    const int fpkw = srt_form_int("pkw", 1);
+    const int pkw = rix && D <= 31 && n <= 32768 ? (fpkw == 2 ? 2 : fpkw != 0) : 0;
     uint8_t* l8 = NULL;
     if (!pkw) {
         LVL_ALLOC(l8, (size_t)nrows * ld);
@@ -2942,8 +3168,9 @@ int srt_levels_build(const srt_comm* comm, int n, int ld, int row0, int nrows, i
     return SRT_OK;
 }
 
-/* the held build's post pass: 1 srt_levels_pred's packed words with levels + a transpose +
- * rel_pk_kernel, 0 the u8 level rows + rel_tree_kernel */
+/* the held build's post pass: 1 srt_levels_pred's source-major packed words with levels +
+ * rel_pk_kernel, 2 its target-major words + a transpose + rel_pk_kernel, 0 the u8 level rows +
+ * rel_tree_kernel */
 int srt_levels_pkw_ready(void) {
     const lvl_state* L = &g_lvl[srt_state_slot()];
     return L->held ? L->pkw : 0;
@@ -2955,7 +3182,8 @@ int srt_levels_pkw_ready(void) {
  * 32768: half the bytes of the predecessor slab and its transpose), else int32. */
 int srt_levels_pred(void* predT, int pred16, double* rT, size_t ldp, unsigned long long* ties,
                     int32_t* pn_over, int* pn_cap, hipStream_t st) {
-    /* pred16 == 2: the packed form (srt_levels_rtab) */
+    /* pred16 == 2: the packed form (srt_levels_rtab); 3: the packed form source-major, predT the
+     * rows pk[local source][target] of stride ldp (lvl_pred_rows_kernel; no tie count) */
     lvl_state* L = &g_lvl[srt_state_slot()];
     if (!L->held) {
         srt_set_error("levels: no held level build for the predecessor pass");
@@ -2970,8 +3198,12 @@ int srt_levels_pred(void* predT, int pred16, double* rT, size_t ldp, unsigned lo
         srt_set_error("levels: int16 predecessors need n <= 32768 (n = %d)", L->n);
         return SRT_E_ARG;
     }
-    if (pred16 == 2 && !L->rix) {
+    if (pred16 >= 2 && !L->rix) {
         srt_set_error("levels: the packed form needs the reliability table");
+        return SRT_E_ARG;
+    }
+    if (pred16 == 3 && (ties || L->D > 31)) {
+        srt_set_error("levels: the source-major packed words take no tie count and at most 31 levels");
         return SRT_E_ARG;
     }
     /* The Delta_1 groups from the in-arc runs first (lvl_pred_near_kernel), where the runs pay:
@@ -3008,7 +3240,13 @@ int srt_levels_pred(void* predT, int pred16, double* rT, size_t ldp, unsigned lo
         SRT_HIPCHK(hipGetLastError());
         *pn_cap = cap;
     }
-    if (pred16 == 2)
+    if (pred16 == 3) { /* narrow units: the packed words straight into the source-major rows */
+        const unsigned ntg = (unsigned)srt_ceil_div(L->n, 32);
+        const unsigned nunit = ntg * (unsigned)srt_ceil_div(L->nw, 16);
+        lvl_pred_rows_kernel<<<lvl_grid((const void*)lvl_pred_rows_kernel, nunit, 0, 512), 512, 0, st>>>(
+            L->n, L->nw, L->nchunk, L->row0, L->nrows, L->D, ntg, nunit, L->off, L->arcs, L->aoff, L->rix,
+            L->lev, (uint32_t*)predT, ldp, bkt, bcnt, cap);
+    } else if (pred16 == 2)
         lvl_pred_kernel<uint32_t><<<lvl_grid((const void*)lvl_pred_kernel<uint32_t>, L->nblk), 256, 0, st>>>(
             L->n, L->nw, L->nchunk, L->row0, L->nrows, L->D, L->nblk, L->off, L->arcs, L->aoff, L->ar,
             L->rix, L->lev, (uint32_t*)predT, rT, ldp, part, bkt, bcnt, cap);

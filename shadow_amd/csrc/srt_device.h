@@ -168,12 +168,15 @@ int srt_levels_build(const srt_comm* comm, int n, int ld, int row0, int nrows, i
                      hipStream_t st, evpool_t* evp, int* levels, int64_t* gather_bytes);
 /* predecessors (int16 when pred16, else int32) + arc reliabilities of the held level build
  * (target-major, row stride ldp). *pn_cap: the bucket capacity of lvl_pred_near_kernel's pre-pass
- * (0: not taken); it adds its overflowed buckets to the device word pn_over */
+ * (0: not taken); it adds its overflowed buckets to the device word pn_over. pred16 = 2: packed
+ * words, target-major; pred16 = 3: the same words source-major, predT[local source][target] with
+ * row stride ldp (no transpose after it; ties must be NULL) */
 int srt_levels_pred(void* predT, int pred16, double* rT, size_t ldp, unsigned long long* ties,
                     int32_t* pn_over, int* pn_cap, hipStream_t st);
-/* 1 when the held level build's post pass is the packed-word form (srt_levels_pred with pred16 = 2:
- * pred | reliability index << 16 | level << 27 per pair, one transpose, then rel_pk_kernel writes
- * the u32 rows too); 0: the u8 level rows + srt_levels_pred + rel_tree_kernel */
+/* nonzero when the held level build's post pass is the packed-word form (pred | reliability
+ * index << 16 | level << 27 per pair, then rel_pk_kernel writes the u32 rows too): 1 the words
+ * source-major (srt_levels_pred with pred16 = 3), 2 target-major (pred16 = 2) and one transpose;
+ * 0: the u8 level rows + srt_levels_pred + rel_tree_kernel */
 int srt_levels_pkw_ready(void);
 /* frees the held level build (stream-ordered) */
 void srt_levels_release(hipStream_t st);
