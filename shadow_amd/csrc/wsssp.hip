@@ -391,9 +391,11 @@ int srt_wsssp_rows(int n, int directed, const int2* rowptr, const uint2* cw, con
  * lives in a private relabelled f64 row (L2 / Infinity Cache), the output rows are written once
  * at the end with whole lines. Same Dial bucket order, settle-time canonical
  * predecessor argmin (D[u], arc rank) and path-order reliability as wsssp_kernel, so the tables
- * are identical. A distance above 1022 quanta or a full bucket flags the source, which the caller
- * recomputes with the wave kernel; the caller only picks this form when a probe source shows every
- * distance fits (d(a, b) <= 2 ecc(s0)). Undirected graphs only.
+ * are identical. A full bucket flags the source, and so does a distance above 1022 quanta: such a
+ * vertex keeps the code 1023 beside a reached neighbour, which the output pass finds. The caller
+ * recomputes flagged sources with the wave kernel. It only picks this form when a probe source
+ * shows every distance of its own component fits (d(a, b) <= 2 ecc(s0)); another component's
+ * rows may still pass 1022 and rest on the flag. Undirected graphs only.
  * ------------------------------------------------------------------------------------------ */
 #define WG_INF 1023u
 /* arc windows in flight per lane. Same-box C5 A/Bs: 3 beat 4 by 1.1%, 2 beat 3 by 0.3%, and 1 and
@@ -727,10 +729,10 @@ __global__ __launch_bounds__(WG) void wgsssp_kernel(
                         const uint32_t du = (wu >> (10 * (u % 3))) & 1023u;
                         const uint32_t dow = d + (uint32_t)(c0 + own[j] >= n0); /* owner's D */
                         const uint32_t nd = dow + wk;
+                        /* du is a 10-bit field, so nd < du fits it; a candidate of 1023 or more
+                         * leaves u unreached here and is found at the end of the source */
                         if (nd < du) {
-                            if (nd >= WG_INF) {
-                                s_ovf = 1; /* not representable in 10 bits */
-                            } else if (wg_lower(sd, u, nd, wu)) {
+                            if (wg_lower(sd, u, nd, wu)) {
                                 const int b2 = (int)(nd & bm);
                                 const int slot = (int)atomicAdd(&bcnt[b2], 1u);
                                 if (slot < bcap) {
@@ -831,6 +833,19 @@ __global__ __launch_bounds__(WG) void wgsssp_kernel(
                 rr[i] = ld_coherent(relp + v);
             else if (dv == WG_INF)
                 rr[i] = 0.0; /* unreached */
+            /* a vertex left unreached beside a reached one is 1023 quanta or more away (any
+             * smaller candidate would have lowered it): its distance does not fit the packed
+             * row, the source is flagged. On a shortest path the first vertex past 1022 has a
+             * predecessor settled at <= 1022 and is never lowered, so no such row is missed, and
+             * no row that fits is flagged. Connected graphs never enter the scan */
+            if (dv == WG_INF) {
+                const int2 be = rowptr[v];
+                for (int k = be.x; k < be.y; ++k)
+                    if (wg_get(sd, CMP ? cc[k].x & 0x1FFFFu : ca[k].x) != WG_INF) {
+                        overflow[orow] = 1;
+                        break;
+                    }
+            }
         }
         if (s_ovf && tid == 0) overflow[orow] = 1;
         __syncthreads();
