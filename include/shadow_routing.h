@@ -278,6 +278,79 @@ int srt_build_routes(const srt_edges* g, const srt_build_opts* opts, int32_t nsr
                      const int32_t* srcs, int32_t* pred, int32_t* first_hop, int32_t* hops,
                      srt_route_stats* stats);
 
+/* ---- link load: traffic per arc from the routes and a demand (linkload.hip) -----------------
+ * Given demands c(s, t) (u64) and the canonical routes above:
+ *   load(u -> t)  the sum of c(s, x) over the pairs whose route from s crosses the arc u -> t
+ *   through(v)    the sum of c(s, x) over the pairs whose route has v strictly inside
+ * Demand that carries no load is counted, not dropped: at t == s it goes to self_demand (the
+ * diagonal's path-to-self routes are not exported), at an unreachable t to unrouted; routed is the
+ * rest, and the sum of load over the arcs equals the sum of c(s, t) * hops(s, t) over the routed
+ * pairs. Every sum is u64; a demand whose total does not fit u64 is refused (SRT_E_RANGE), so
+ * nothing wraps. */
+typedef struct srt_link_load {
+    int64_t narcs;
+    int32_t *tail, *head;
+    uint64_t* load;    /* arcs with load > 0, by (tail, head) */
+    uint64_t* through; /* n */
+    uint64_t routed, unrouted, self_demand;
+    double ms_tables, ms_routes, ms_load; /* ms_load: HIP events around the load pass alone */
+    int32_t max_hops; /* deepest route of the rows that carried routed demand */
+    int32_t forms;    /* bit f-1 set when some row's flow words took form f */
+} srt_link_load;
+/* the load pass of a device entry point */
+typedef struct srt_link_load_stats {
+    double ms_load;
+    int32_t max_hops, forms;
+} srt_link_load_stats;
+
+/* Largest n whose flow words (one per target of a row) live in LDS as u32 (form 1: rows whose
+ * routed demand is below 2^32) or as u64 (form 2); form 3 keeps u64 words in device memory, and
+ * its value is the largest n the pass takes at all. A row without routed demand takes no form. */
+int srt_link_load_stage_max_n(int form);
+/* Device entry point: every pointer is a device pointer. Row i of pred and hops (stride ldp: the
+ * rows srt_routes_rows_device wrote for the same sources) and of the u64 demand rows dem (stride
+ * ldd) belongs to srcs[i], or src_begin + i when srcs is NULL. The pass ADDS into load (one word
+ * per in-arc of the graph, srt_sparse_graph_info's arc count, in the order of
+ * srt_sparse_graph_in_arcs), through (n words) and totals (routed, unrouted, self): the caller
+ * zeroes them before the first call and keeps the total demand within u64. Returns after the
+ * stream. */
+int srt_link_load_rows_device(const srt_sparse_graph* g, int32_t nsrc, const int32_t* srcs,
+                              int32_t src_begin, const int32_t* pred, const int32_t* hops,
+                              size_t ldp, const uint64_t* dem, size_t ldd, uint64_t* load,
+                              uint64_t* through, uint64_t* totals, void* stream,
+                              srt_link_load_stats* stats);
+/* the in-arc CSR load is indexed by: device pointers owned by the graph (rowptr: n + 1 offsets by
+ * head, tails: the tail of every position) */
+int srt_sparse_graph_in_arcs(const srt_sparse_graph* g, const int32_t** rowptr,
+                             const int32_t** tails);
+/* Rows [row0, row0 + nrows) of a dense device graph and its finished lat table (as for
+ * srt_routes_dense_device, whose pred and hops rows, stride ldp, it takes): load is indexed by the
+ * essential in-arc CSR, which the call compacts and copies out -- rowptr (n + 1 offsets by head),
+ * tails and load hold arc_cap positions (SRT_E_RANGE when the graph has more essential arcs:
+ * srt_route_stats.ess_arcs says how many; *narcs receives the number). The call zeroes load,
+ * through and totals itself. */
+int srt_link_load_dense_device(int32_t n, int32_t ld, int32_t directed, const uint32_t* w,
+                               const uint32_t* lat, int32_t row0, int32_t nrows,
+                               const int32_t* pred, const int32_t* hops, size_t ldp,
+                               const uint64_t* dem, size_t ldd, int64_t arc_cap, int32_t* rowptr,
+                               int32_t* tails, uint64_t* load, int64_t* narcs, uint64_t* through,
+                               uint64_t* totals, void* stream, srt_link_load_stats* stats);
+/* The link load of a demand on a host edge list. One GPU; the same choice of algorithm, chunks,
+ * front ends and refusals as srt_build_routes (a graph whose distances need u64 rows:
+ * SRT_E_RANGE).
+ *   ndem < 0   uniform: demand 1 from every source of srcs (nsrc of them, strictly increasing;
+ *              NULL with nsrc = n: every vertex) to every vertex
+ *   ndem >= 0  COO demands (dsrc, dtgt, dval), grouped by source in increasing order (targets in
+ *              any order, duplicates add); the sources are the distinct dsrc; srcs must be NULL
+ *              and nsrc is ignored
+ * The demand rows are built chunk by chunk on the device: no nsrc x n host matrix exists.
+ * use_shortest_path = 0: load(s -> t) = c(s, t), through = 0, on the host (SRT_E_INVALID unless
+ * the graph is complete). *out is freed with srt_link_load_free. */
+int srt_build_link_load(const srt_edges* g, const srt_build_opts* opts, int32_t nsrc,
+                        const int32_t* srcs, int64_t ndem, const int32_t* dsrc,
+                        const int32_t* dtgt, const uint64_t* dval, srt_link_load** out);
+void srt_link_load_free(srt_link_load* ll);
+
 /* ---- multi-GPU (one process per GPU; RCCL over xGMI) ----------------------------------- */
 typedef struct srt_comm srt_comm;
 /* 128-byte RCCL unique id, created on rank 0 and shared by the caller (e.g. torch.distributed). */

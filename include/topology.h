@@ -136,6 +136,17 @@ int64_t srt_topology_route_string_ip(Topology* top, uint32_t srcIpNet, uint32_t 
                                      char* buf, size_t cap);
 /* srt_build_routes calls this topology has made (diagnostic: rows are built once) */
 int32_t srt_topology_route_builds(Topology* top);
+/* ---- link load (linkload.hip): the packet counters charged to the arcs of their routes ------
+ * A snapshot of the counters (relaxed loads) becomes the demand of srt_build_link_load: a counter
+ * belongs to the served path (from, to) -- srt_topology_path_source_ip's vertex first -- and its
+ * packets are charged to the arcs of route(from, to) in that direction, as the reference keeps one
+ * Path object and one packet count per pair whichever way it was looked up. Self-path counters
+ * land in self_demand. Like a route query the call records no pair-order lookup, changes no
+ * counter, offers nothing to the runahead hook and does not touch the route rows. *out is freed
+ * with srt_link_load_free. */
+int srt_topology_link_load(Topology* top, srt_link_load** out);
+/* srt_build_link_load calls this topology has made (diagnostic) */
+int32_t srt_topology_link_load_builds(Topology* top);
 /* Graph facts established by validation (topology.c:659-716). */
 int32_t srt_topology_vertex_count(Topology* top);
 int64_t srt_topology_edge_count(Topology* top);

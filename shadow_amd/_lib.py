@@ -89,6 +89,32 @@ class RouteStats(ctypes.Structure):
     ]
 
 
+class LinkLoad(ctypes.Structure):
+    _fields_ = [
+        ("narcs", ctypes.c_int64),
+        ("tail", ctypes.POINTER(ctypes.c_int32)),
+        ("head", ctypes.POINTER(ctypes.c_int32)),
+        ("load", ctypes.POINTER(ctypes.c_uint64)),
+        ("through", ctypes.POINTER(ctypes.c_uint64)),
+        ("routed", ctypes.c_uint64),
+        ("unrouted", ctypes.c_uint64),
+        ("self_demand", ctypes.c_uint64),
+        ("ms_tables", ctypes.c_double),
+        ("ms_routes", ctypes.c_double),
+        ("ms_load", ctypes.c_double),
+        ("max_hops", ctypes.c_int32),
+        ("forms", ctypes.c_int32),
+    ]
+
+
+class LinkLoadStats(ctypes.Structure):
+    _fields_ = [
+        ("ms_load", ctypes.c_double),
+        ("max_hops", ctypes.c_int32),
+        ("forms", ctypes.c_int32),
+    ]
+
+
 # (name, restype, argtypes) for every exported symbol of the C-ABI
 _VP, _I32, _I64, _U32, _U64, _D, _CP = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
                                          ctypes.c_uint32, ctypes.c_uint64, ctypes.c_double,
@@ -123,6 +149,15 @@ SIGNATURES = {
     "srt_routes_dense_device": (ctypes.c_int, [_I32, _I32, _I32, _VP, _VP, _I32, _I32, _VP, _VP, _VP,
                                                 ctypes.c_size_t, _VP, _VP]),
     "srt_build_routes": (ctypes.c_int, [_VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP]),
+    "srt_link_load_stage_max_n": (ctypes.c_int, [ctypes.c_int]),
+    "srt_link_load_rows_device": (ctypes.c_int, [_VP, _I32, _VP, _I32, _VP, _VP, ctypes.c_size_t, _VP,
+                                                  ctypes.c_size_t, _VP, _VP, _VP, _VP, _VP]),
+    "srt_sparse_graph_in_arcs": (ctypes.c_int, [_VP, _VP, _VP]),
+    "srt_link_load_dense_device": (ctypes.c_int, [_I32, _I32, _I32, _VP, _VP, _I32, _I32, _VP, _VP,
+                                                   ctypes.c_size_t, _VP, ctypes.c_size_t, _I64, _VP,
+                                                   _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "srt_build_link_load": (ctypes.c_int, [_VP, _VP, _I32, _VP, _I64, _VP, _VP, _VP, _VP]),
+    "srt_link_load_free": (None, [_VP]),
     "srt_comm_unique_id": (ctypes.c_int, [_VP]),
     "srt_comm_init": (ctypes.c_int, [_VP, _I32, _I32, _I32, _VP]),
     "srt_comm_init_all": (ctypes.c_int, [_I32, _VP, _VP]),
@@ -183,6 +218,8 @@ SIGNATURES = {
     "srt_topology_route_ip": (_I32, [_VP, _U32, _U32, _VP, _I32]),
     "srt_topology_route_string_ip": (_I64, [_VP, _U32, _U32, _VP, ctypes.c_size_t]),
     "srt_topology_route_builds": (_I32, [_VP]),
+    "srt_topology_link_load": (ctypes.c_int, [_VP, _VP]),
+    "srt_topology_link_load_builds": (_I32, [_VP]),
     "srt_topology_vertex_count": (_I32, [_VP]),
     "srt_topology_edge_count": (_I64, [_VP]),
     "srt_topology_is_directed": (ctypes.c_int, [_VP]),

@@ -2375,3 +2375,476 @@ extern "C" int srt_build_routes(const srt_edges* g, const srt_build_opts* opts, 
     }
     return rc;
 }
+
+/* ------------------------------------------------------------------------------------------ */
+/* Link load (linkload.hip): the route pass over each chunk of rows, then the load pass over    */
+/* the pred and hops rows it wrote and the chunk's demand rows, which are built on the device.  */
+/* ------------------------------------------------------------------------------------------ */
+extern "C" int srt_sparse_graph_in_arcs(const srt_sparse_graph* g, const int32_t** rowptr,
+                                        const int32_t** tails) {
+    if (!g) {
+        srt_set_error("srt_sparse_graph_in_arcs: null graph");
+        return SRT_E_ARG;
+    }
+    if (rowptr) *rowptr = g->irp;
+    if (tails) *tails = g->icol;
+    return SRT_OK;
+}
+
+extern "C" int srt_link_load_rows_device(const srt_sparse_graph* g, int32_t nsrc,
+                                         const int32_t* srcs, int32_t src_begin,
+                                         const int32_t* pred, const int32_t* hops, size_t ldp,
+                                         const uint64_t* dem, size_t ldd, uint64_t* load,
+                                         uint64_t* through, uint64_t* totals, void* stream,
+                                         srt_link_load_stats* stats) {
+    if (!g || nsrc < 1 || (!srcs && (src_begin < 0 || (int64_t)src_begin + nsrc > g->n))) {
+        srt_set_error("srt_link_load_rows_device: bad arguments");
+        return SRT_E_ARG;
+    }
+    srt_link_load_stats local;
+    memset(&local, 0, sizeof(local));
+    const int rc = srt_link_load_rows(g->n, nsrc, srcs, src_begin, pred, hops, ldp, dem, ldd, g->irp,
+                                      g->icol, load, through, 1, totals, (hipStream_t)stream,
+                                      &local.max_hops, &local.forms, &local.ms_load);
+    if (!rc && stats) *stats = local;
+    return rc;
+}
+
+extern "C" int srt_link_load_dense_device(int32_t n, int32_t ld, int32_t directed, const uint32_t* w,
+                                          const uint32_t* lat, int32_t row0, int32_t nrows,
+                                          const int32_t* pred, const int32_t* hops, size_t ldp,
+                                          const uint64_t* dem, size_t ldd, int64_t arc_cap,
+                                          int32_t* rowptr, int32_t* tails, uint64_t* load,
+                                          int64_t* narcs, uint64_t* through, uint64_t* totals,
+                                          void* stream, srt_link_load_stats* stats) {
+    if (n < 1 || ld < n || !w || !lat || row0 < 0 || nrows < 1 || (int64_t)row0 + nrows > n ||
+        arc_cap < 0 || !rowptr || !tails || !load || !through || !totals) {
+        srt_set_error("srt_link_load_dense_device: bad arguments (n = %d, ld = %d, rows [%d, %d))", n,
+                      ld, row0, row0 + nrows);
+        return SRT_E_ARG;
+    }
+    if (n > SRT_DENSE_MAX_N) {
+        srt_set_error("srt_link_load_dense_device: n = %d beyond the dense limit %d", n,
+                      SRT_DENSE_MAX_N);
+        return SRT_E_RANGE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    srt_link_load_stats local;
+    memset(&local, 0, sizeof(local));
+    int32_t *irp = NULL, *icol = NULL;
+    uint32_t* iw = NULL;
+    int64_t arcs = 0;
+    double ms_ess = 0;
+    int rc = srt_routes_ess_build(n, ld, directed, w, lat, st, &irp, &icol, &iw, &arcs, &ms_ess);
+    if (!rc && narcs) *narcs = arcs;
+    if (!rc && arcs > arc_cap) {
+        srt_set_error("srt_link_load_dense_device: %lld essential arcs, room for %lld",
+                      (long long)arcs, (long long)arc_cap);
+        rc = SRT_E_RANGE;
+    }
+    if (!rc) {
+        TRYHIP(hipMemcpyAsync(rowptr, irp, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        TRYHIP(hipMemcpyAsync(tails, icol, (size_t)arcs * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        TRYHIP(hipMemsetAsync(load, 0, (size_t)arcs * sizeof(uint64_t), st));
+        TRYHIP(hipMemsetAsync(through, 0, (size_t)n * sizeof(uint64_t), st));
+        TRYHIP(hipMemsetAsync(totals, 0, 3 * sizeof(uint64_t), st));
+        /* an undirected graph's essential lists are compacted in column order, a directed one's
+         * through per-head cursors in no order */
+        rc = srt_link_load_rows(n, nrows, NULL, row0, pred, hops, ldp, dem, ldd, irp, icol, load,
+                                through, directed ? 0 : 1, totals, st, &local.max_hops,
+                                &local.forms, &local.ms_load);
+    }
+out:
+    srt_routes_ess_free(irp, icol, iw, st);
+    if (!rc && stats) *stats = local;
+    return rc;
+}
+
+extern "C" void srt_link_load_free(srt_link_load* ll) {
+    if (!ll) return;
+    free(ll->tail);
+    free(ll->head);
+    free(ll->load);
+    free(ll->through);
+    free(ll);
+}
+
+/* an all-zero result over n vertices with room for narcs arcs */
+static srt_link_load* link_load_new(int64_t n, int64_t narcs) {
+    srt_link_load* ll = (srt_link_load*)calloc(1, sizeof(srt_link_load));
+    if (!ll) return NULL;
+    const size_t na = (size_t)(narcs > 0 ? narcs : 1);
+    ll->tail = (int32_t*)malloc(na * sizeof(int32_t));
+    ll->head = (int32_t*)malloc(na * sizeof(int32_t));
+    ll->load = (uint64_t*)malloc(na * sizeof(uint64_t));
+    ll->through = (uint64_t*)calloc((size_t)(n > 0 ? n : 1), sizeof(uint64_t));
+    if (!ll->tail || !ll->head || !ll->load || !ll->through) {
+        srt_link_load_free(ll);
+        return NULL;
+    }
+    return ll;
+}
+
+/* the demand of a call: uniform over the sources verts (NULL: every vertex), or COO entries whose
+ * distinct sources are verts, row i holding the entries [rowptr[i], rowptr[i + 1]) */
+struct ll_demand {
+    int32_t nsub;
+    const int32_t* verts;
+    const int64_t* rowptr; /* NULL: uniform */
+    const int32_t* tgt;
+    const uint64_t* val;
+};
+
+/* the positions of a by-head CSR that carry load, as (tail, head, load) sorted by (tail, head) */
+static int link_load_collect(int n, const int32_t* irp, const int32_t* icol, const uint64_t* load,
+                             srt_link_load* ll) {
+    const int64_t na = irp[n];
+    std::vector<int64_t> start((size_t)n + 1, 0);
+    int64_t cnt = 0;
+    for (int64_t k = 0; k < na; k++)
+        if (load[k]) {
+            start[(size_t)icol[k] + 1]++;
+            cnt++;
+        }
+    for (int v = 0; v < n; v++) start[(size_t)v + 1] += start[v];
+    const size_t room = (size_t)(cnt > 0 ? cnt : 1);
+    int32_t* tail = (int32_t*)malloc(room * sizeof(int32_t));
+    int32_t* head = (int32_t*)malloc(room * sizeof(int32_t));
+    uint64_t* ld = (uint64_t*)malloc(room * sizeof(uint64_t));
+    if (!tail || !head || !ld) {
+        free(tail);
+        free(head);
+        free(ld);
+        srt_set_error("srt_build_link_load: out of memory for %lld arcs", (long long)cnt);
+        return SRT_E_NOMEM;
+    }
+    /* heads ascend in the outer loop, so each tail's arcs come out by head */
+    for (int t = 0; t < n; t++)
+        for (int64_t k = irp[t]; k < irp[t + 1]; k++)
+            if (load[k]) {
+                const int64_t o = start[icol[k]]++;
+                tail[o] = icol[k];
+                head[o] = t;
+                ld[o] = load[k];
+            }
+    free(ll->tail);
+    free(ll->head);
+    free(ll->load);
+    ll->tail = tail;
+    ll->head = head;
+    ll->load = ld;
+    ll->narcs = cnt;
+    return SRT_OK;
+}
+
+/* one GPU: routes_one's loop with the load pass behind the route pass of every chunk */
+static int link_load_one(const srt_canon* c, const srt_build_opts* opts, int algo,
+                         const ll_demand* dm, srt_link_load* ll) {
+    const int n = c->n;
+    const int nsub = dm->nsub;
+    const int32_t* verts = dm->verts;
+    const int dev = opts ? opts->device : 0;
+    srt_route_stats local;
+    memset(&local, 0, sizeof(local));
+    srt_build_stats bs;
+    memset(&bs, 0, sizeof(bs));
+    dbufs B;
+    B.k = 0;
+    hipStream_t st = NULL;
+    int32_t* dverts = NULL;
+    int32_t *dpred = NULL, *dhops = NULL, *dtgt = NULL;
+    int64_t* drowptr = NULL;
+    uint64_t *ddem = NULL, *dval = NULL, *dload = NULL, *dthrough = NULL, *dtot = NULL;
+    uint32_t *dw = NULL, *dlat = NULL, *iw = NULL;
+    double *dr = NULL, *drel = NULL;
+    int32_t *irp = NULL, *icol = NULL;
+    const int32_t *lirp = NULL, *licol = NULL; /* the CSR the load is indexed by */
+    int64_t narcs = 0, max_ent = 0;
+    srt_sparse_graph* sg = NULL;
+    const bool dense = algo == SRT_ALGO_DENSE_FW;
+    const int ld = srt_ceil_div(n, 128) * 128;
+    /* per row: the distance and reliability rows (sparse), pred, hops and the u64 demand */
+    const size_t per_row = (size_t)n * ((dense ? 0 : 12) + 8 + 8);
+    int chunk = nsub;
+    int32_t forms = 0, mh = 0;
+    uint64_t htot[3] = {0, 0, 0};
+    std::vector<int32_t> hirp, hicol;
+    std::vector<uint64_t> hload;
+    std::vector<int64_t> rel_rowptr;
+    int rc = SRT_OK;
+    TRYHIP(hipSetDevice(dev));
+    TRYHIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    if (verts) {
+        TRY(dalloc(&B, (void**)&dverts, (size_t)nsub * sizeof(int32_t)));
+        TRYHIP(hipMemcpyAsync(dverts, verts, (size_t)nsub * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    }
+    if (dense) {
+        if (n > SRT_DENSE_MAX_N) {
+            srt_set_error("dense build supports n <= %d (n = %d); use the sparse SSSP",
+                          SRT_DENSE_MAX_N, n);
+            rc = SRT_E_RANGE;
+            goto out;
+        }
+        const size_t ll2 = (size_t)ld * ld;
+        TRY(dalloc(&B, (void**)&dw, ll2 * sizeof(uint32_t)));
+        TRY(dalloc(&B, (void**)&dr, ll2 * sizeof(double)));
+        TRY(dalloc(&B, (void**)&dlat, ll2 * sizeof(uint32_t)));
+        TRY(dalloc(&B, (void**)&drel, ll2 * sizeof(double)));
+        TRY(dense_upload(c, ld, 0, ld, dw, dr, st, 1));
+        TRY(srt_dense_build_device_ms(n, ld, c->directed, dw, dr, dlat, drel, NULL, c->quantum_ns, st,
+                                      opts ? opts->fw_block : 0, &bs));
+        local.ms_tables = bs.ms_total;
+        TRY(srt_routes_ess_build(n, ld, c->directed, dw, dlat, st, &irp, &icol, &iw, &narcs,
+                                 &local.ms_routes));
+        lirp = irp;
+        licol = icol;
+    } else {
+        TRY(sparse_graph_from_canon(c, dev, &sg));
+        lirp = sg->irp;
+        licol = sg->icol;
+        narcs = sg->arcs;
+    }
+    {
+        const size_t cb = chunk_budget((size_t)narcs * 8, 1) / per_row;
+        chunk = (int)(cb < (size_t)nsub ? (cb > 0 ? cb : 1) : (size_t)nsub);
+    }
+    if (!dense) {
+        TRY(dalloc(&B, (void**)&dlat, (size_t)chunk * n * sizeof(uint32_t)));
+        TRY(dalloc(&B, (void**)&drel, (size_t)chunk * n * sizeof(double)));
+    }
+    TRY(dalloc(&B, (void**)&dpred, (size_t)chunk * n * sizeof(int32_t)));
+    TRY(dalloc(&B, (void**)&dhops, (size_t)chunk * n * sizeof(int32_t)));
+    TRY(dalloc(&B, (void**)&ddem, (size_t)chunk * n * sizeof(uint64_t)));
+    TRY(dalloc(&B, (void**)&dload, (size_t)narcs * sizeof(uint64_t)));
+    TRY(dalloc(&B, (void**)&dthrough, (size_t)n * sizeof(uint64_t)));
+    TRY(dalloc(&B, (void**)&dtot, 3 * sizeof(uint64_t)));
+    TRYHIP(hipMemsetAsync(dload, 0, (size_t)narcs * sizeof(uint64_t), st));
+    TRYHIP(hipMemsetAsync(dthrough, 0, (size_t)n * sizeof(uint64_t), st));
+    TRYHIP(hipMemsetAsync(dtot, 0, 3 * sizeof(uint64_t), st));
+    if (dm->rowptr) { /* room for the COO entries of the largest chunk */
+        for (int r0 = 0; r0 < nsub; r0 += chunk) {
+            const int r1 = r0 + chunk < nsub ? r0 + chunk : nsub;
+            const int64_t e = dm->rowptr[r1] - dm->rowptr[r0];
+            max_ent = e > max_ent ? e : max_ent;
+        }
+        TRY(dalloc(&B, (void**)&drowptr, ((size_t)chunk + 1) * sizeof(int64_t)));
+        TRY(dalloc(&B, (void**)&dtgt, (size_t)max_ent * sizeof(int32_t)));
+        TRY(dalloc(&B, (void**)&dval, (size_t)max_ent * sizeof(uint64_t)));
+        rel_rowptr.resize((size_t)chunk + 1);
+    }
+    for (int r0 = 0; r0 < nsub; r0 += chunk) {
+        const int cnt = r0 + chunk < nsub ? chunk : nsub - r0;
+        const int32_t* cs = verts ? dverts + r0 : NULL;
+        if (dense) {
+            TRY(srt_routes_rows_timed(n, cnt, cs, r0, 1, dlat, (size_t)ld, irp, icol, iw, dpred, NULL,
+                                      dhops, (size_t)n, st, &local));
+        } else {
+            memset(&bs, 0, sizeof(bs));
+            TRY(verts ? sparse_rows(sg, 0, cnt, cs, dlat, drel, NULL, st, &bs)
+                      : sparse_rows(sg, r0, r0 + cnt, NULL, dlat, drel, NULL, st, &bs));
+            local.ms_tables += bs.ms_total;
+            TRY(srt_routes_rows_timed(n, cnt, cs, r0, 0, dlat, (size_t)n, sg->irp, sg->icol, sg->iw,
+                                      dpred, NULL, dhops, (size_t)n, st, &local));
+        }
+        if (dm->rowptr) {
+            const int64_t e0 = dm->rowptr[r0], ne = dm->rowptr[r0 + cnt] - e0;
+            for (int i = 0; i <= cnt; i++) rel_rowptr[i] = dm->rowptr[r0 + i] - e0;
+            TRYHIP(hipMemcpyAsync(drowptr, rel_rowptr.data(), ((size_t)cnt + 1) * sizeof(int64_t),
+                                  hipMemcpyHostToDevice, st));
+            if (ne > 0) {
+                TRYHIP(hipMemcpyAsync(dtgt, dm->tgt + e0, (size_t)ne * sizeof(int32_t),
+                                      hipMemcpyHostToDevice, st));
+                TRYHIP(hipMemcpyAsync(dval, dm->val + e0, (size_t)ne * sizeof(uint64_t),
+                                      hipMemcpyHostToDevice, st));
+            }
+            TRYHIP(hipStreamSynchronize(st)); /* rel_rowptr is reused by the next chunk */
+        }
+        TRY(srt_link_load_demand_rows(n, cnt, drowptr, dtgt, dval, ddem, (size_t)n, st));
+        TRY(srt_link_load_rows(n, cnt, cs, r0, dpred, dhops, (size_t)n, ddem, (size_t)n, lirp, licol,
+                               dload, dthrough, dense && c->directed ? 0 : 1, dtot, st, &mh, &forms,
+                               &ll->ms_load));
+    }
+    hirp.resize((size_t)n + 1);
+    hicol.resize((size_t)(narcs > 0 ? narcs : 1));
+    hload.resize((size_t)(narcs > 0 ? narcs : 1));
+    TRYHIP(hipMemcpyAsync(hirp.data(), lirp, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (narcs > 0) {
+        TRYHIP(hipMemcpyAsync(hicol.data(), licol, (size_t)narcs * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        TRYHIP(hipMemcpyAsync(hload.data(), dload, (size_t)narcs * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    }
+    TRYHIP(hipMemcpyAsync(ll->through, dthrough, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    TRYHIP(hipMemcpyAsync(htot, dtot, sizeof(htot), hipMemcpyDeviceToHost, st));
+    TRYHIP(hipStreamSynchronize(st));
+    TRY(link_load_collect(n, hirp.data(), hicol.data(), hload.data(), ll));
+    ll->routed = htot[0];
+    ll->unrouted = htot[1];
+    ll->self_demand = htot[2];
+    ll->ms_tables = local.ms_tables;
+    ll->ms_routes = local.ms_routes;
+    ll->max_hops = mh;
+    ll->forms = forms;
+out:
+    if (st) {
+        srt_routes_ess_free(irp, icol, iw, st);
+        (void)hipStreamSynchronize(st);
+        (void)hipStreamDestroy(st);
+    }
+    srt_sparse_graph_free(sg);
+    dfree(&B);
+    return rc;
+}
+
+/* direct mode (topology.c:1816-1858): every pair is its own edge, so load(s -> t) = c(s, t) */
+static int link_load_direct(const srt_edges* g, const ll_demand* dm, srt_link_load* ll) {
+    const int n = g->n;
+    std::vector<int32_t> tail, head;
+    std::vector<uint64_t> load, row;
+    if (dm->rowptr) row.assign((size_t)n, 0);
+    for (int32_t i = 0; i < dm->nsub; i++) {
+        const int32_t s = dm->verts ? dm->verts[i] : i;
+        if (dm->rowptr) {
+            for (int64_t k = dm->rowptr[i]; k < dm->rowptr[i + 1]; k++) row[dm->tgt[k]] += dm->val[k];
+        }
+        for (int32_t t = 0; t < n; t++) {
+            const uint64_t cst = dm->rowptr ? row[t] : 1;
+            if (dm->rowptr) row[t] = 0;
+            if (!cst) continue;
+            if (t == s) {
+                ll->self_demand += cst;
+                continue;
+            }
+            ll->routed += cst;
+            tail.push_back(s);
+            head.push_back(t);
+            load.push_back(cst);
+        }
+    }
+    const size_t k = tail.size();
+    if (k) {
+        int32_t* nt = (int32_t*)realloc(ll->tail, k * sizeof(int32_t));
+        if (nt) ll->tail = nt;
+        int32_t* nh = (int32_t*)realloc(ll->head, k * sizeof(int32_t));
+        if (nh) ll->head = nh;
+        uint64_t* nl = (uint64_t*)realloc(ll->load, k * sizeof(uint64_t));
+        if (nl) ll->load = nl;
+        if (!nt || !nh || !nl) {
+            srt_set_error("srt_build_link_load: out of memory for %zu arcs", k);
+            return SRT_E_NOMEM;
+        }
+        memcpy(ll->tail, tail.data(), k * sizeof(int32_t));
+        memcpy(ll->head, head.data(), k * sizeof(int32_t));
+        memcpy(ll->load, load.data(), k * sizeof(uint64_t));
+    }
+    ll->narcs = (int64_t)k;
+    ll->max_hops = k ? 1 : 0;
+    return SRT_OK;
+}
+
+extern "C" int srt_build_link_load(const srt_edges* g, const srt_build_opts* opts, int32_t nsrc,
+                                   const int32_t* srcs, int64_t ndem, const int32_t* dsrc,
+                                   const int32_t* dtgt, const uint64_t* dval, srt_link_load** out) {
+    if (out) *out = NULL;
+    if (!g || g->n <= 0 || !out) {
+        srt_set_error("srt_build_link_load: null argument");
+        return SRT_E_ARG;
+    }
+    const int n = g->n;
+    ll_demand dm = {0, NULL, NULL, NULL, NULL};
+    std::vector<int32_t> dverts;
+    std::vector<int64_t> rowptr;
+    if (ndem < 0) {
+        if (check_verts(n, nsrc, srcs)) {
+            srt_set_error("srt_build_link_load: the sources must be 1..n strictly increasing vertex "
+                          "indices (or NULL with nsrc = n)");
+            return SRT_E_ARG;
+        }
+        dm.nsub = nsrc;
+        dm.verts = srcs;
+    } else {
+        if (srcs || (ndem > 0 && (!dsrc || !dtgt || !dval))) {
+            srt_set_error("srt_build_link_load: COO demands take their sources from dsrc (srcs must "
+                          "be NULL) and need all three arrays");
+            return SRT_E_ARG;
+        }
+        uint64_t total = 0;
+        for (int64_t k = 0; k < ndem; k++) {
+            if (dsrc[k] < 0 || dsrc[k] >= n || dtgt[k] < 0 || dtgt[k] >= n ||
+                (k && dsrc[k] < dsrc[k - 1])) {
+                srt_set_error("srt_build_link_load: demand %lld: vertices within [0, %d), grouped by "
+                              "source in increasing order", (long long)k, n);
+                return SRT_E_ARG;
+            }
+            if (total + dval[k] < total) {
+                srt_set_error("srt_build_link_load: the total demand passes 2^64 - 1 at entry %lld",
+                              (long long)k);
+                return SRT_E_RANGE;
+            }
+            total += dval[k];
+            if (!k || dsrc[k] != dsrc[k - 1]) {
+                dverts.push_back(dsrc[k]);
+                rowptr.push_back(k);
+            }
+        }
+        rowptr.push_back(ndem);
+        dm.nsub = (int32_t)dverts.size();
+        dm.verts = dm.nsub == n ? NULL : dverts.data(); /* n distinct sources: every vertex */
+        dm.rowptr = rowptr.data();
+        dm.tgt = dtgt;
+        dm.val = dval;
+    }
+    srt_link_load* ll = link_load_new(n, 0);
+    if (!ll) {
+        srt_set_error("srt_build_link_load: out of memory");
+        return SRT_E_NOMEM;
+    }
+    int rc = SRT_OK;
+    const int use_sp = opts ? opts->use_shortest_path : 1;
+    if (!use_sp) {
+        int32_t* const none[3] = {NULL, NULL, NULL};
+        rc = routes_direct(g, 0, NULL, none); /* the completeness check and its error */
+        if (!rc) rc = link_load_direct(g, &dm, ll);
+    } else if (dm.nsub == 0) {
+        rc = SRT_OK; /* no demand: nothing to route */
+    } else if (srt_device_count() < 1) {
+        srt_set_error("srt_build_link_load: no HIP device");
+        rc = SRT_E_DEVICE;
+    } else {
+        /* the table build's own route to an algorithm, as srt_build_routes */
+        const int forced = opts ? opts->algo : SRT_ALGO_AUTO;
+        int edge_form = 0;
+        if (forced != SRT_ALGO_SPARSE_SSSP && g->n <= SRT_DENSE_MAX_N && g->m > 0) {
+            const double nn = g->n, ub = (double)g->m * (g->directed ? 1 : 2);
+            edge_form = g->n <= 2048 || ub * 16.0 >= nn * nn || forced == SRT_ALGO_DENSE_FW;
+        }
+        for (int attempt = 0; attempt < 2; attempt++) {
+            srt_canon c;
+            if (edge_form && attempt == 0 && canon_from_edges(g, &c) == 0) {
+                c.verify_dense = forced != SRT_ALGO_DENSE_FW;
+            } else {
+                if (attempt == 0) edge_form = 0;
+                rc = srt_canon_build(g, &c);
+                if (rc) break;
+            }
+            const int algo = c.wide && forced != SRT_ALGO_DENSE_FW ? SRT_ALGO_SPARSE_SSSP
+                                                                    : choose_algo(&c, opts);
+            if (c.wide) {
+                srt_set_error("srt_build_link_load: shortest-path latencies may pass the u32 range "
+                              "(bound %llu quanta of %llu ns); the route pass reads u32 rows only",
+                              (unsigned long long)c.dist_bound, (unsigned long long)c.quantum_ns);
+                srt_canon_free(&c);
+                rc = SRT_E_RANGE;
+                break;
+            }
+            ll->ms_load = 0;
+            rc = link_load_one(&c, opts, algo, &dm, ll);
+            srt_canon_free(&c);
+            if (rc != SRT_FALLBACK_CANON) break;
+        }
+    }
+    if (rc) {
+        srt_link_load_free(ll);
+        return rc;
+    }
+    *out = ll;
+    return SRT_OK;
+}

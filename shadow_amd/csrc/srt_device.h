@@ -290,6 +290,20 @@ int srt_routes_ess_build(int n, int ld, int directed, const uint32_t* w, const u
                          hipStream_t st, int32_t** irp, int32_t** icol, uint32_t** iw,
                          int64_t* arcs, double* ms);
 void srt_routes_ess_free(int32_t* irp, int32_t* icol, uint32_t* iw, hipStream_t st);
+/* linkload.hip: the load pass over nrows rows of pred / hops (stride ldp) and u64 demand (stride
+ * ldd) against an in-arc CSR: ADDS into load (one word per CSR position), through (n) and totals
+ * (routed, unrouted, self); sorted != 0 promises in-lists with ascending tails (a sparse graph's,
+ * an undirected dense graph's: binary search; else the lists are scanned); raises *max_hops, ors the flow forms into *forms, adds the HIP-event
+ * time of the kernel to *ms. Returns after the stream. */
+int srt_link_load_rows(int n, int nrows, const int32_t* srcs, int src_begin, const int32_t* pred,
+                       const int32_t* hops, size_t ldp, const uint64_t* dem, size_t ldd,
+                       const int32_t* irp, const int32_t* icol, uint64_t* load, uint64_t* through,
+                       int sorted, uint64_t* totals, hipStream_t st, int32_t* max_hops,
+                       int32_t* forms, double* ms);
+/* demand rows of a chunk: 1 everywhere (rowptr NULL), or the COO entries [rowptr[r], rowptr[r + 1])
+ * of row r added into zeroed rows (tgt, val: device arrays those offsets index) */
+int srt_link_load_demand_rows(int n, int nrows, const int64_t* rowptr, const int32_t* tgt,
+                              const uint64_t* val, uint64_t* dem, size_t ldd, hipStream_t st);
 /* collectives: all-gather of equal byte blocks, rank q's block at buf + q * bytes */
 int srt_coll_allgather(const srt_comm* c, void* buf, size_t bytes, hipStream_t st);
 

@@ -339,6 +339,7 @@ struct _Topology {
     struct route_batch* route_batches;
     int route_failed;
     atomic_int route_builds; /* srt_build_routes calls made */
+    atomic_int link_load_builds; /* srt_build_link_load calls made */
     _Atomic(struct arc_index*) arcs; /* (from, to) -> canonical edge, built on the first string */
 };
 
@@ -1830,4 +1831,69 @@ int64_t srt_topology_route_string_ip(Topology* t, uint32_t srcIp, uint32_t dstIp
 #undef ROUTE_PUT
     free(verts);
     return len;
+}
+
+/* ---- link load: the packet counters charged to the arcs of their routes -------------------- *
+ * A counter belongs to the served Path (from, to) (path.c:57-59), so its packets are charged to
+ * the arcs of route(from, to) in that direction, whichever way the pair was looked up. The
+ * counter pages are read with relaxed loads into COO demands, sources ascending as the pages are
+ * walked; self paths land in self_demand. Like a route query this records no pair-order lookup,
+ * changes no counter, offers nothing to the runahead hook and leaves the route rows alone. */
+int srt_topology_link_load(Topology* t, srt_link_load** out) {
+    if (out) *out = NULL;
+    if (!magic_ok(t) || !out) return SRT_E_ARG;
+    cntmap_t* m = &t->counters;
+    int64_t cap = 1024, k = 0;
+    int32_t* dsrc = (int32_t*)malloc((size_t)cap * sizeof(int32_t));
+    int32_t* dtgt = (int32_t*)malloc((size_t)cap * sizeof(int32_t));
+    uint64_t* dval = (uint64_t*)malloc((size_t)cap * sizeof(uint64_t));
+    int rc = dsrc && dtgt && dval ? SRT_OK : SRT_E_NOMEM;
+    for (int32_t from = 0; !rc && from < m->n; from++) {
+        _Atomic(_Atomic uint64_t*)* d = atomic_load_explicit(&m->dir[from], memory_order_acquire);
+        if (!d) continue;
+        for (int32_t p = 0; !rc && p < m->npages; p++) {
+            _Atomic uint64_t* pg = atomic_load_explicit(&d[p], memory_order_acquire);
+            if (!pg) continue;
+            for (int32_t i = 0; i < CNT_PAGE && p * CNT_PAGE + i < m->n; i++) {
+                const uint64_t c = atomic_load_explicit(&pg[i], memory_order_relaxed);
+                if (!c) continue;
+                if (k == cap) {
+                    cap *= 2;
+                    int32_t* ns = (int32_t*)realloc(dsrc, (size_t)cap * sizeof(int32_t));
+                    if (ns) dsrc = ns;
+                    int32_t* nt = (int32_t*)realloc(dtgt, (size_t)cap * sizeof(int32_t));
+                    if (nt) dtgt = nt;
+                    uint64_t* nv = (uint64_t*)realloc(dval, (size_t)cap * sizeof(uint64_t));
+                    if (nv) dval = nv;
+                    if (!ns || !nt || !nv) {
+                        rc = SRT_E_NOMEM;
+                        break;
+                    }
+                }
+                dsrc[k] = from;
+                dtgt[k] = p * CNT_PAGE + i;
+                dval[k] = c;
+                k++;
+            }
+        }
+    }
+    if (rc) {
+        srt_set_error("out of memory for the packet-counter snapshot");
+    } else {
+        srt_edges e;
+        srt_topology_edges(t, &e);
+        srt_build_opts o = t->opts;
+        o.use_shortest_path = t->use_shortest_path;
+        rc = srt_build_link_load(&e, &o, 0, NULL, k, dsrc, dtgt, dval, out);
+        atomic_fetch_add(&t->link_load_builds, 1);
+        if (rc) srt_log(SRT_LOG_ERROR, "link-load build failed (%d): %s", rc, srt_last_error());
+    }
+    free(dsrc);
+    free(dtgt);
+    free(dval);
+    return rc;
+}
+
+int32_t srt_topology_link_load_builds(Topology* t) {
+    return magic_ok(t) ? atomic_load(&t->link_load_builds) : -1;
 }

@@ -23,7 +23,7 @@ import struct
 import numpy as np
 
 from . import _lib
-from ._lib import BuildOpts, BuildStats, Edges, RouteStats, check, lib
+from ._lib import BuildOpts, BuildStats, Edges, LinkLoad, LinkLoadStats, RouteStats, check, lib
 
 
 def ip_to_net(ip) -> int:
@@ -284,6 +284,17 @@ class Topology:
     def route_builds(self) -> int:
         return lib().srt_topology_route_builds(self._h)
 
+    # -- link load -----------------------------------------------------------------------------
+    def link_load(self):
+        """srt_topology_link_load: the packet counters charged to the arcs of their routes ->
+        (tail, head, load, through, stats) as build_link_load returns them."""
+        out = ctypes.POINTER(LinkLoad)()
+        check(lib().srt_topology_link_load(self._h, ctypes.byref(out)), "srt_topology_link_load")
+        return _take_link_load(out, self.n)
+
+    def link_load_builds(self) -> int:
+        return lib().srt_topology_link_load_builds(self._h)
+
 
 MIN_HOOK = ctypes.CFUNCTYPE(None, ctypes.c_double)
 
@@ -381,6 +392,83 @@ def build_routes(n, directed, src, dst, lat_ns, loss, sources=None, use_shortest
     return pred, first, hops, st
 
 
+class LinkLoadInfo:
+    """The scalar fields of srt_link_load."""
+
+    def __init__(self, ll):
+        for name in ("routed", "unrouted", "self_demand", "ms_tables", "ms_routes", "ms_load",
+                     "max_hops", "forms"):
+            setattr(self, name, getattr(ll, name))
+        self.narcs = int(ll.narcs)
+
+
+def _take_link_load(out, n):
+    """(tail int32 [k], head int32 [k], load u64 [k], through u64 [n], LinkLoadInfo) copied out of
+    an srt_link_load, which is freed."""
+    ll = out.contents
+    k = int(ll.narcs)
+    arr = lambda p, m, dt: (np.ctypeslib.as_array(p, (m,)).astype(dt) if m else np.zeros(0, dt))
+    res = (arr(ll.tail, k, np.int32), arr(ll.head, k, np.int32), arr(ll.load, k, np.uint64),
+           arr(ll.through, n, np.uint64), LinkLoadInfo(ll))
+    lib().srt_link_load_free(out)
+    return res
+
+
+def demand_coo(demand, sources, n):
+    """A dense [k, n] demand (row i belongs to sources[i], or to vertex i when sources is None) as
+    the COO triple srt_build_link_load takes: grouped by source, sources increasing."""
+    d = np.asarray(demand)
+    if d.ndim != 2 or d.shape[1] != n:
+        raise ValueError(f"a dense demand is [k, {n}], got {d.shape}")
+    if (d < 0).any():
+        raise ValueError("demands are unsigned")
+    ss = np.arange(n) if sources is None else np.asarray(sources)
+    if len(ss) != d.shape[0] or (np.diff(ss) <= 0).any():
+        raise ValueError("one demand row per source, the sources strictly increasing")
+    r, t = np.nonzero(d)
+    return ss[r].astype(np.int32), t.astype(np.int32), d[r, t].astype(np.uint64)
+
+
+def build_link_load(n, directed, src, dst, lat_ns, loss, sources=None, demand=None,
+                    use_shortest_path=True, device=0, algo=_lib.ALGO_AUTO):
+    """srt_build_link_load on host arrays -> (tail, head, load, through, stats): the arcs that carry
+    load by (tail, head), the u64 load of each, the u64 transit traffic of every vertex, and the
+    totals, times, max_hops and forms (LinkLoadInfo).
+    demand: None -- 1 from every source of `sources` (strictly increasing; None = every vertex)
+    to every vertex; a dense [k, n] array (row i = sources[i]); or a COO triple (dsrc, dtgt, dval)
+    grouped by source in increasing order (duplicates add; `sources` must be None)."""
+    src = np.ascontiguousarray(src, np.int32)
+    dst = np.ascontiguousarray(dst, np.int32)
+    lat_ns = np.ascontiguousarray(lat_ns, np.int64)
+    loss = np.ascontiguousarray(loss, np.float64)
+    e = Edges(n, int(bool(directed)), len(src), src.ctypes.data, dst.ctypes.data,
+              lat_ns.ctypes.data, loss.ctypes.data)
+    o = BuildOpts(device, algo, int(bool(use_shortest_path)), 0)
+    out = ctypes.POINTER(LinkLoad)()
+    if demand is None:
+        ss = None if sources is None else np.ascontiguousarray(sources, np.int32)
+        rc = lib().srt_build_link_load(ctypes.byref(e), ctypes.byref(o), n if ss is None else len(ss),
+                                       None if ss is None else ss.ctypes.data, -1, None, None, None,
+                                       ctypes.byref(out))
+    else:
+        if isinstance(demand, tuple):
+            if sources is not None:
+                raise ValueError("COO demands name their own sources")
+            dsrc, dtgt, dval = demand
+        else:
+            dsrc, dtgt, dval = demand_coo(demand, sources, n)
+        dsrc = np.ascontiguousarray(dsrc, np.int32)
+        dtgt = np.ascontiguousarray(dtgt, np.int32)
+        dval = np.ascontiguousarray(dval, np.uint64)
+        if not len(dsrc) == len(dtgt) == len(dval):
+            raise ValueError("the COO arrays differ in length")
+        rc = lib().srt_build_link_load(ctypes.byref(e), ctypes.byref(o), 0, None, len(dsrc),
+                                       dsrc.ctypes.data, dtgt.ctypes.data, dval.ctypes.data,
+                                       ctypes.byref(out))
+    check(rc, "srt_build_link_load")
+    return _take_link_load(out, n)
+
+
 class SparseGraph:
     """Device-resident canonical CSR (srt_sparse_graph_*): rows of any source range are computed
     on the device into caller-provided device buffers (torch tensors or raw pointers)."""
@@ -431,6 +519,28 @@ class SparseGraph:
                                            self.n if ldo is None else int(ldo),
                                            ctypes.c_void_p(stream), st),
               "srt_routes_rows_device")
+
+    def in_arcs(self):
+        """Device pointers (rowptr, tails) of the in-arc CSR that link_load_rows' load indexes."""
+        rp, tl = ctypes.c_void_p(), ctypes.c_void_p()
+        check(lib().srt_sparse_graph_in_arcs(self._h, ctypes.byref(rp), ctypes.byref(tl)),
+              "srt_sparse_graph_in_arcs")
+        return rp.value, tl.value
+
+    def link_load_rows(self, nsrc, pred_ptr, hops_ptr, dem_ptr, load_ptr, through_ptr, totals_ptr,
+                       srcs_ptr=None, src_begin=0, ldp=None, ldd=None, stream=None, stats=None):
+        """srt_link_load_rows_device over device pointers: adds the rows' load into load (arcs u64),
+        through (n u64) and totals (3 u64), which the caller zeroes."""
+        st = ctypes.byref(stats) if stats is not None else None
+        check(lib().srt_link_load_rows_device(self._h, int(nsrc), ctypes.c_void_p(srcs_ptr),
+                                              int(src_begin), ctypes.c_void_p(pred_ptr),
+                                              ctypes.c_void_p(hops_ptr),
+                                              self.n if ldp is None else int(ldp),
+                                              ctypes.c_void_p(dem_ptr),
+                                              self.n if ldd is None else int(ldd),
+                                              ctypes.c_void_p(load_ptr), ctypes.c_void_p(through_ptr),
+                                              ctypes.c_void_p(totals_ptr), ctypes.c_void_p(stream), st),
+              "srt_link_load_rows_device")
 
     def free(self):
         if getattr(self, "_h", None):
