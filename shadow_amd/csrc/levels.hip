@@ -1822,49 +1822,60 @@ __global__ __launch_bounds__(256, 7) void lvl_pred_kernel(int n, int nw, int nch
 }
 
 /* The packed words source-major, no transpose (the packed form without the tie count): narrow
- * units. A wave covers 4 targets x 16 words (512 sources), 16 lanes per target: lane (g, l) owns
- * word c16 * 16 + l of target 32 * tg + 4 * wave + g. A workgroup's eight waves hold 32
- * consecutive targets of one 512-source sub-chunk, so after the walk each source has a full
- * 128-B run of its row (32 targets x 4 B) in the workgroup: the walk's sidx entries are the
- * staging tile, and the output stage stores whole lines of pk[source][target] (row stride ld).
+ * units, a template over the unit shape -- TPW targets per wave (64 / TPW words, lanes, per
+ * target), NWV waves per workgroup, PB gathers per pipelined batch. The shape in use is <4, 4, 8>:
+ * a wave covers 4 targets x 16 words (512 sources), 16 lanes per target: lane (g, l) owns word
+ * c16 * 16 + l of target 16 * tg + 4 * wave + g. A workgroup's four waves hold 16 consecutive
+ * targets of one 512-source sub-chunk, so after the walk each source has a 64-B run of its row
+ * (16 targets x 4 B) in the workgroup: the walk's sidx entries are the staging tile, and the
+ * output stage stores whole runs of pk[source][target] (row stride ld).
  * The gathered slices are 64 B, and a pass over all targets touches n x 64 B per plane (2 MB on
- * C4) where the 2,048-source units touch 8 MB; the walk itself is slower than the wide one (C4:
- * 5.3-5.5 against 4.1 ms, L2 hit rate 0.40 against 0.51: four times the units re-read the arc
- * offsets and the buckets) by less than the 1.65-ms transpose it removes. The rule, the words
- * and the walk's order are lvl_pred_unit's; what differs:
- *  - the in-arc group bounds and the walk's position are per 16-lane group; a group past its
- *    bound or without a pending source has its gathers predicated off; the wave leaves a weight
- *    when every group has, and a level when no lane has a pending source;
- *  - a group's next LVL_PB arc offsets come with one vector load (lane l takes arc l of its
+ * C4) where the 2,048-source units touch 8 MB; the walk itself is slower than the wide one (four
+ * times the units re-read the arc offsets and the buckets) by less than the 1.65-ms transpose it
+ * removes. The walk is bound by gather latency times waves in flight, so the shape is the one
+ * that holds seven waves per SIMD: 256-thread workgroups of 22,784 B of LDS (seven per CU) and
+ * 70 VGPRs without scratch (C4 5.5-5.6 ms against 5.9-6.0 for eight-wave workgroups
+ * at six waves per SIMD; PB 10 and 12 and 8 targets x 8 words per wave measured and dropped).
+ * The rule, the words and the walk's order are lvl_pred_unit's; what differs:
+ *  - the in-arc group bounds and the walk's position are per lane group of a target; a group past
+ *    its bound or without a pending source has its gathers predicated off; the wave leaves a
+ *    weight when every group has, and a level when no lane has a pending source;
+ *  - a group's next PB arc offsets come with one vector load (lane l takes arc l of its
  *    group) and reach the lanes by a cross-lane read inside the group (ds_bpermute), so no
  *    register is held per in-flight gather for them;
  *  - the direct arcs (w == d): lane l tests arc i0 + l of its group against the pending word of
  *    the lane that owns the arc's source (one ds_bpermute) and writes that lane's sidx entry and
  *    claimed bit through LDS;
  *  - lvl_pred_near_kernel's buckets stay keyed by (target, 2,048-source chunk): a group reads
- *    the bucket of its enclosing chunk and keeps the entries of its 512 sources.
- * LDS per lane, LVL_RW_LANE = 24 words: 16 of sidx (32 u16), the claimed word (after the walk
- * the five level planes, words 16..20), and three spare words that hold the target's group
- * bounds (off[t][l], [16 + l], [32 + l]: weight w's bound is in lane w & 15, word 21 + (w >> 4)).
- * A target's 16 lanes and 4 words of padding are LVL_RW_TGT = 388 words; 32 targets are 49,664 B,
- * three workgroups of 512 threads per CU (six waves per SIMD). */
-#define LVL_RW_LANE 24
-#define LVL_RW_TGT (16 * LVL_RW_LANE + 4)
-__global__ __launch_bounds__(512, 6) void lvl_pred_rows_kernel(int n, int nw, int nchunk, int src0, int nsrc,
-                                                                int nlev, unsigned ntg, unsigned nunit,
-                                                                const int32_t* __restrict__ off,
-                                                                const uint32_t* __restrict__ arcs,
-                                                                const uint32_t* __restrict__ aoff,
-                                                                const uint16_t* __restrict__ rix,
-                                                                const uint32_t* __restrict__ lev,
-                                                                uint32_t* __restrict__ pk, size_t ld,
-                                                                const uint32_t* __restrict__ bkt,
-                                                                const uint32_t* __restrict__ bcnt, int cap) {
-    __shared__ __attribute__((aligned(16))) uint32_t sw[32 * LVL_RW_TGT];
-    const int lane = threadIdx.x & 63, l = lane & 15;
+ *    the bucket of its enclosing chunk and keeps the entries of its sub-chunk's sources.
+ * LDS per lane, LVL_RW_LANE = 22 words: 16 of sidx (32 u16) and the claimed word; words 17.. are
+ * idle during the walk and hold the target's group bounds off[t][0 .. 32] (31 levels at most:
+ * weight w's bound is in lane w % WPT, word 17 + w / WPT); after the walk, behind a wave-level
+ * sync (a target never leaves its wave), the five level planes take words 16..20. A target's
+ * lanes are followed by 4 words of padding, the first of which keeps off[t][0] for the output
+ * stage. A lane's words are 8-B aligned (88 B apart), so the tile is accessed in 8-B pieces; the
+ * 16 lanes of a target start on the 16 even banks of 32 (24 words apart they shared 4), two
+ * targets of a 32-lane group 4 banks apart share them two ways. The output stage's 8-B plane
+ * reads are conflict-free (quads 4 x 356 words apart: 16 banks of 64; words 22 apart), its 4-B
+ * sidx reads two-way (quads 16 banks of 32 apart). */
+#define LVL_RW_LANE 22
+template <int TPW, int NWV, int PB>
+__global__ __launch_bounds__(NWV * 64, NWV == 4 ? 7 : 6) void lvl_pred_rows_kernel(
+    int n, int nw, int nchunk, int src0, int nsrc, int nlev, unsigned ntg, unsigned nunit,
+    const int32_t* __restrict__ off, const uint32_t* __restrict__ arcs, const uint32_t* __restrict__ aoff,
+    const uint16_t* __restrict__ rix, const uint32_t* __restrict__ lev, uint32_t* __restrict__ pk, size_t ld,
+    const uint32_t* __restrict__ bkt, const uint32_t* __restrict__ bcnt, int cap) {
+    constexpr int WPT = 64 / TPW;                 /* words (lanes) per target */
+    constexpr int NT = TPW * NWV;                  /* targets per workgroup */
+    constexpr int SUB = WPT * 32;                  /* sources per sub-chunk */
+    constexpr int TGT = WPT * LVL_RW_LANE + 4;     /* a target's words: its lanes' and the padding */
+    constexpr int NB = (33 + WPT - 1) / WPT;       /* bound words per lane: off[t][0 .. 32] */
+    static_assert(PB <= WPT && NB <= 5 && NT % 4 == 0 && (NT / 4) * (SUB / 8) == NWV * 64, "unit shape");
+    __shared__ __attribute__((aligned(16))) uint32_t sw[NT * TGT];
+    const int lane = threadIdx.x & 63, l = lane & (WPT - 1);
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int gl = wv * 4 + (lane >> 4); /* the lane's target inside the workgroup's 32 */
-    uint32_t* tgt = sw + gl * LVL_RW_TGT;
+    const int gl = wv * TPW + lane / WPT; /* the lane's target inside the workgroup's NT */
+    uint32_t* tgt = sw + gl * TGT;
     uint32_t* mine = tgt + l * LVL_RW_LANE;
     uint16_t* my = reinterpret_cast<uint16_t*>(mine);
     const size_t plane = (size_t)n * nw;
@@ -1873,43 +1884,43 @@ __global__ __launch_bounds__(512, 6) void lvl_pred_rows_kernel(int n, int nw, in
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     };
-    /* p anywhere in the lane's 16-lane group (every lane of the wave calls it) */
+    /* p anywhere in the lane's WPT-lane group (every lane of the wave calls it) */
     auto gany = [&](bool p) -> bool {
-        return ((__ballot(p) >> (lane & 48)) & 0xFFFFull) != 0ull;
+        return ((__ballot(p) >> (lane & (64 - WPT))) & ((1ull << WPT) - 1ull)) != 0ull;
     };
     /* chunk-major, consecutive workgroups (one per XCD in turn) on consecutive target groups:
      * the whole GPU gathers from one sub-chunk's slices at a time */
     for (unsigned u = blockIdx.x; u < nunit; u += gridDim.x) {
         const int c16 = (int)(u / ntg), tg = (int)(u % ntg);
-        const int t = tg * 32 + gl, word = c16 * 16 + l;
+        const int t = tg * NT + gl, word = c16 * WPT + l;
         const bool tv = t < n, act = tv && word < nw;
-        const int cs0 = c16 * 512; /* the sub-chunk's first local source */
+        const int cs0 = c16 * SUB; /* the sub-chunk's first local source */
 #pragma unroll
-        for (int q = 0; q < 16; q += 4)
-            *reinterpret_cast<uint4*>(mine + q) = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
+        for (int q = 0; q < 16; q += 2) /* (a lane's words are 8-B aligned: 22 words apart) */
+            *reinterpret_cast<uint2*>(mine + q) = make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
         mine[16] = 0u;
         {
             const int32_t* ot = off + (size_t)(tv ? t : 0) * LVL_STRIDE;
-            mine[21] = tv ? (uint32_t)ot[l] : 0u;
-            mine[22] = tv ? (uint32_t)ot[16 + l] : 0u;
-            mine[23] = tv ? (uint32_t)ot[32 + l] : 0u;
+#pragma unroll
+            for (int k = 0; k < NB; ++k) mine[17 + k] = tv ? (uint32_t)ot[k * WPT + l] : 0u;
+            if (l == 0) tgt[WPT * LVL_RW_LANE] = tv ? (uint32_t)ot[0] : 0u;
         }
         wave_sync();
-        auto otl = [&](int w) -> int { return (int)tgt[(w & 15) * LVL_RW_LANE + 21 + (w >> 4)]; };
+        auto otl = [&](int w) -> int { return (int)tgt[(w & (WPT - 1)) * LVL_RW_LANE + 17 + w / WPT]; };
         const int a_t = otl(0);
         const uint32_t lane4 = (uint32_t)(act ? word : 0) * 4u;
         /* the bucket of (t, enclosing chunk): the entries of this sub-chunk's sources into
          * their owners' sidx slots and claimed words. An overflowed bucket is ignored. */
         bool pn = false;
         if (bkt) {
-            const size_t un = (size_t)(tv ? t : 0) * nchunk + (c16 >> 2);
+            const size_t un = (size_t)(tv ? t : 0) * nchunk + c16 / (2048 / SUB);
             const int k = tv ? (int)bcnt[un] : cap + 1;
             pn = k <= cap;
             const uint32_t* ub = bkt + un * cap;
-            for (int i = l; pn && i < k; i += 16) {
+            for (int i = l; pn && i < k; i += WPT) {
                 const uint32_t e = ub[i], sl = e & 2047u;
-                if ((int)(sl >> 9) != (c16 & 3)) continue;
-                uint32_t* o = tgt + ((sl >> 5) & 15u) * LVL_RW_LANE;
+                if ((int)(sl / SUB) != (c16 & (2048 / SUB - 1))) continue;
+                uint32_t* o = tgt + ((sl >> 5) & (uint32_t)(WPT - 1)) * LVL_RW_LANE;
                 reinterpret_cast<uint16_t*>(o)[sl & 31u] = (uint16_t)(e >> 11);
                 atomicOr(&o[16], 1u << (sl & 31u));
             }
@@ -1932,12 +1943,12 @@ __global__ __launch_bounds__(512, 6) void lvl_pred_rows_kernel(int n, int nw, in
                 if (w == d) {
                     /* the direct arc (u, t): tight for the source u itself; distinct arcs have
                      * distinct sources, so the order does not matter */
-                    for (int i0 = g0; __any(i0 < g1); i0 += 16) {
+                    for (int i0 = g0; __any(i0 < g1); i0 += WPT) {
                         const int i = i0 + l;
                         const int us = i < g1 ? (int)(arcs[i] & 0xFFFFu) - src0 : -1;
-                        const bool in = us >= 0 && us < nsrc && (unsigned)(us - cs0) < 512u;
-                        const int ow = in ? (us >> 5) & 15 : 0;
-                        const uint32_t op = (uint32_t)__shfl((int)pend, ow, 16);
+                        const bool in = us >= 0 && us < nsrc && (unsigned)(us - cs0) < (unsigned)SUB;
+                        const int ow = in ? (us >> 5) & (WPT - 1) : 0;
+                        const uint32_t op = (uint32_t)__shfl((int)pend, ow, WPT);
                         if (in && ((op >> (us & 31)) & 1u)) {
                             uint32_t* o = tgt + ow * LVL_RW_LANE;
                             reinterpret_cast<uint16_t*>(o)[us & 31] = (uint16_t)(i - a_t);
@@ -1947,31 +1958,31 @@ __global__ __launch_bounds__(512, 6) void lvl_pred_rows_kernel(int n, int nw, in
                     wave_sync();
                     pend &= ~mine[16];
                 } else {
-                    /* LVL_PB gathers per batch, software-pipelined as lvl_pred_unit's; e is the
+                    /* PB gathers per batch, software-pipelined as lvl_pred_unit's; e is the
                      * group's end of the walk, pulled in once none of its sources is pending */
                     const char* base = reinterpret_cast<const char*>(lev + (size_t)(d - w - 1) * plane);
                     int i = g0, e = g1;
-                    uint32_t v[LVL_PB], vn[LVL_PB];
+                    uint32_t v[PB], vn[PB];
                     {
-                        const uint32_t aq = l < LVL_PB && i + l < e ? aoff[i + l] : 0u;
+                        const uint32_t aq = l < PB && i + l < e ? aoff[i + l] : 0u;
 #pragma unroll
-                        for (int q = 0; q < LVL_PB; ++q) {
-                            const uint32_t a = (uint32_t)__shfl((int)aq, q, 16);
+                        for (int q = 0; q < PB; ++q) {
+                            const uint32_t a = (uint32_t)__shfl((int)aq, q, WPT);
                             v[q] = i + q < e ? *reinterpret_cast<const uint32_t*>(base + (a + lane4)) : 0u;
                         }
                     }
                     while (__any(i < e)) {
-                        const int i2 = i + LVL_PB;
+                        const int i2 = i + PB;
                         {
-                            const uint32_t aq = l < LVL_PB && i2 + l < e ? aoff[i2 + l] : 0u;
+                            const uint32_t aq = l < PB && i2 + l < e ? aoff[i2 + l] : 0u;
 #pragma unroll
-                            for (int q = 0; q < LVL_PB; ++q) {
-                                const uint32_t a = (uint32_t)__shfl((int)aq, q, 16);
+                            for (int q = 0; q < PB; ++q) {
+                                const uint32_t a = (uint32_t)__shfl((int)aq, q, WPT);
                                 vn[q] = i2 + q < e ? *reinterpret_cast<const uint32_t*>(base + (a + lane4)) : 0u;
                             }
                         }
 #pragma unroll
-                        for (int q = 0; q < LVL_PB; ++q) { /* a source takes its first tight arc */
+                        for (int q = 0; q < PB; ++q) { /* a source takes its first tight arc */
                             uint32_t nb = v[q] & pend;
                             pend &= ~nb;
                             while (nb) {
@@ -1980,7 +1991,7 @@ __global__ __launch_bounds__(512, 6) void lvl_pred_rows_kernel(int n, int nw, in
                             }
                         }
 #pragma unroll
-                        for (int q = 0; q < LVL_PB; ++q) v[q] = vn[q];
+                        for (int q = 0; q < PB; ++q) v[q] = vn[q];
                         i = i2;
                         if (!gany(pend != 0u)) e = min(e, i);
                     }
@@ -1988,39 +1999,44 @@ __global__ __launch_bounds__(512, 6) void lvl_pred_rows_kernel(int n, int nw, in
                 if (!__any(pend != 0u)) break;
             }
         }
+        wave_sync(); /* the bounds' last read (another lane's words 17..) before the planes */
 #pragma unroll
         for (int k = 0; k < 5; ++k) mine[16 + k] = lvb[k];
         __syncthreads();
-        /* Output: thread (wave, k = lane / 8, tq = lane % 8) takes 8 consecutive sources -- bits
-         * oct * 8.. of word wd = 2 * wave + k / 4, oct = k % 4 -- of targets 4 * tq .. + 3: one
-         * 16-B piece per source, the eight tq lanes one source's 128-B run, so every store
-         * instruction writes eight whole lines. nsrc is a multiple of 128: whole groups of 8. */
+        /* Output: thread (tq = thread % NQ, octet = thread / NQ) takes 8 consecutive sources --
+         * bits oct * 8.. of word wd, octet = 4 * wd + oct -- of targets 4 * tq .. + 3: one 16-B
+         * piece per source, the NQ tq lanes one source's run of NT * 4 B, so every store
+         * instruction writes 64 / NQ whole runs with consecutive lanes consecutive in memory.
+         * nsrc is a multiple of 128: whole groups of 8. */
         {
-            const int tq = lane & 7, kq = lane >> 3;
-            const int wd = 2 * wv + (kq >> 2), oct = kq & 3;
-            const int sl0 = cs0 + wd * 32 + oct * 8, t0 = tg * 32 + 4 * tq;
+            constexpr int NQ = NT / 4;
+            const int tq = (int)threadIdx.x % NQ, kq = (int)threadIdx.x / NQ;
+            const int wd = kq >> 2, oct = kq & 3;
+            const int sl0 = cs0 + wd * 32 + oct * 8, t0 = tg * NT + 4 * tq;
             if (sl0 < nsrc && t0 < n) {
-                uint32_t sx[4][4], lq[4][5];
+                uint32_t lq[4][5];
                 int at[4];
+                const uint32_t* ps = sw + (4 * tq) * TGT + wd * LVL_RW_LANE + oct * 4;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const uint32_t* p = sw + (4 * tq + j) * LVL_RW_TGT;
-                    at[j] = (int)p[21];
+                    const uint32_t* p = sw + (4 * tq + j) * TGT;
+                    at[j] = (int)p[WPT * LVL_RW_LANE];
                     p += wd * LVL_RW_LANE;
-                    const uint4 a = *reinterpret_cast<const uint4*>(p + oct * 4);
-                    const uint4 b = *reinterpret_cast<const uint4*>(p + 16);
-                    sx[j][0] = a.x, sx[j][1] = a.y, sx[j][2] = a.z, sx[j][3] = a.w;
-                    lq[j][0] = b.x >> (oct * 8), lq[j][1] = b.y >> (oct * 8);
-                    lq[j][2] = b.z >> (oct * 8), lq[j][3] = b.w >> (oct * 8);
+                    const uint2 b0 = *reinterpret_cast<const uint2*>(p + 16);
+                    const uint2 b1 = *reinterpret_cast<const uint2*>(p + 18);
+                    lq[j][0] = b0.x >> (oct * 8), lq[j][1] = b0.y >> (oct * 8);
+                    lq[j][2] = b1.x >> (oct * 8), lq[j][3] = b1.y >> (oct * 8);
                     lq[j][4] = p[20] >> (oct * 8);
                 }
-#pragma unroll 1 /* (unrolled twice: 80 VGPRs and 32 B of scratch, 6.15 against 5.98 ms) */
+                /* the sidx entries come from the tile a source pair at a time: held in registers
+                 * for all eight sources they are 12 more VGPRs than seven waves per SIMD leave */
+#pragma unroll 1
                 for (int e = 0; e < 8; ++e) {
                     const int sg = src0 + sl0 + e;
                     uint32_t kv[4];
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        const uint32_t x = (sx[j][e >> 1] >> (16 * (e & 1))) & 0xFFFFu;
+                        const uint32_t x = (ps[j * TGT + (e >> 1)] >> (16 * (e & 1))) & 0xFFFFu;
                         const bool h = sg < n && sg != t0 + j && t0 + j < n && x != 0xFFFFu;
                         const int k = at[j] + (h ? (int)x : 0);
                         uint32_t lv = 0;
@@ -3241,9 +3257,11 @@ int srt_levels_pred(void* predT, int pred16, double* rT, size_t ldp, unsigned lo
         *pn_cap = cap;
     }
     if (pred16 == 3) { /* narrow units: the packed words straight into the source-major rows */
-        const unsigned ntg = (unsigned)srt_ceil_div(L->n, 32);
-        const unsigned nunit = ntg * (unsigned)srt_ceil_div(L->nw, 16);
-        lvl_pred_rows_kernel<<<lvl_grid((const void*)lvl_pred_rows_kernel, nunit, 0, 512), 512, 0, st>>>(
+        constexpr int TPW = 4, NWV = 4; /* 16 targets x 512 sources per workgroup of 256 threads */
+        const auto kern = lvl_pred_rows_kernel<TPW, NWV, 8>;
+        const unsigned ntg = (unsigned)srt_ceil_div(L->n, TPW * NWV);
+        const unsigned nunit = ntg * (unsigned)srt_ceil_div(L->nw, 64 / TPW);
+        kern<<<lvl_grid((const void*)kern, nunit, 0, NWV * 64), NWV * 64, 0, st>>>(
             L->n, L->nw, L->nchunk, L->row0, L->nrows, L->D, ntg, nunit, L->off, L->arcs, L->aoff, L->rix,
             L->lev, (uint32_t*)predT, ldp, bkt, bcnt, cap);
     } else if (pred16 == 2)
