@@ -254,6 +254,10 @@ typedef struct srt_route_stats {
  * rows that do not fit as u32 and whose finite entries are all below 0xFFFF); form 3 reads the row
  * from global memory, and its value is the largest n the pass takes at all. */
 int srt_routes_stage_max_n(int form);
+/* Test diagnostic: the largest number of row chunks any row loop of the last srt_build_* call
+ * took (tables, routes or link load; the rank threads of a multi-rank build included). Each
+ * srt_build_* entry resets it, so it is not meaningful while builds run concurrently. */
+int srt_last_row_chunks(void);
 /* Device entry points: every pointer is a device pointer, any of the three outputs may be NULL,
  * outputs have row stride ldo (>= n; columns >= n are never written), `stream` as above. The
  * calls return after their work on the stream has finished.

@@ -144,6 +144,7 @@ SIGNATURES = {
     "srt_sparse_graph_rows_list": (ctypes.c_int, [_VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP]),
     "srt_sparse_graph_free": (None, [_VP]),
     "srt_routes_stage_max_n": (ctypes.c_int, [ctypes.c_int]),
+    "srt_last_row_chunks": (ctypes.c_int, []),
     "srt_routes_rows_device": (ctypes.c_int, [_VP, _I32, _VP, _I32, _VP, ctypes.c_size_t, _VP, _VP,
                                                _VP, ctypes.c_size_t, _VP, _VP]),
     "srt_routes_dense_device": (ctypes.c_int, [_I32, _I32, _I32, _VP, _VP, _I32, _I32, _VP, _VP, _VP,

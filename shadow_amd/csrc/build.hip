@@ -23,6 +23,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <atomic>
 #include <vector>
 
 #include "srt_device.h"
@@ -1072,10 +1073,14 @@ static int check_verts(int n, int nsub, const int32_t* verts) {
 
 /* device memory for row chunks after `reserved` bytes: what is free beyond a 12 GiB reserve,
  * capped at 48 GiB; when less than that reserve is free, half of what is free. `sharers` ranks
- * (virtual ranks on one device) read the same free figure at once, so each takes its share. */
+ * (virtual ranks on one device) read the same free figure at once, so each takes its share.
+ * SRT_FORM memcap (MiB, a test hook) stands in for the free figure, as in the level build. */
 static size_t chunk_budget(size_t reserved, int sharers) {
     size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
+    const int cap_mb = srt_form_int("memcap", -1);
+    if (cap_mb >= 0) {
+        free_b = (size_t)cap_mb << 20;
+    } else if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
         (void)hipGetLastError();
         return (size_t)1 << 30;
     }
@@ -1088,6 +1093,41 @@ static size_t chunk_budget(size_t reserved, int sharers) {
     }
     return budget / (size_t)(sharers > 1 ? sharers : 1);
 }
+
+/* how many of nrows rows of per_row bytes that budget holds at a time: at least one */
+static int chunk_rows(size_t reserved, int sharers, size_t per_row, int nrows) {
+    const size_t cb = chunk_budget(reserved, sharers) / per_row;
+    return (int)(cb < (size_t)nrows ? (cb > 0 ? cb : 1) : (size_t)nrows);
+}
+
+/* the full-width rows of the sources at slots [r0, r0 + cnt) of a build: the vertices the device
+ * list dverts holds there, or the vertices [r0, r0 + cnt) themselves without a list. The one place
+ * that knows sparse_rows' two source conventions. */
+static int sparse_chunk(const srt_sparse_graph* sg, const int32_t* dverts, int r0, int cnt,
+                        uint32_t* lat_rows, double* rel_rows, double* lms, hipStream_t st,
+                        srt_build_stats* stats) {
+    return dverts ? sparse_rows(sg, 0, cnt, dverts + r0, lat_rows, rel_rows, lms, st, stats)
+                  : sparse_rows(sg, r0, r0 + cnt, NULL, lat_rows, rel_rows, lms, st, stats);
+}
+
+/* the size limit of every dense form (srt_dense_max_n) */
+static int check_dense_n(int n) {
+    if (n <= SRT_DENSE_MAX_N) return SRT_OK;
+    srt_set_error("dense build supports n <= %d (n = %d); use the sparse SSSP", SRT_DENSE_MAX_N, n);
+    return SRT_E_RANGE;
+}
+
+/* the row chunks of the last srt_build_* call (srt_last_row_chunks, a test diagnostic): reset by
+ * each entry, raised by each of its row loops -- rank threads included -- to its own count */
+static std::atomic<int> last_row_chunks{0};
+
+static void note_row_chunks(int k) {
+    int cur = last_row_chunks.load(std::memory_order_relaxed);
+    while (cur < k && !last_row_chunks.compare_exchange_weak(cur, k, std::memory_order_relaxed)) {
+    }
+}
+
+extern "C" int srt_last_row_chunks(void) { return last_row_chunks.load(std::memory_order_relaxed); }
 
 /* ------------------------------------------------------------------------------------------ */
 /* Host <-> device staging of the dense matrices and the tables. No n x n host matrix is built:  */
@@ -1503,17 +1543,86 @@ static int table_download(void* dst, size_t dpitch, const void* src, size_t spit
     return rc;
 }
 
-/* the nsub x nsub sub-tables (contiguous on the device) into the caller's buffers */
-static int download_sub(int nsub, const uint32_t* slat, const double* srel, const double* sms,
-                        uint32_t* lat_q, double* rel, double* lat_ms, hipStream_t st,
-                        srt_build_stats* local) {
-    SRT_HIPCHK(hipStreamSynchronize(st)); /* the transfer alone is timed */
+/* rows x ncols of the device tables (row stride ld entries) into the caller's host tables (row
+ * stride ncols), after the work already on `st`: the transfer alone is timed */
+static int download_tables(int rows, int ncols, int ld, const uint32_t* dlat, const double* drel,
+                           const double* dms, uint32_t* lat_q, double* rel, double* lat_ms,
+                           hipStream_t st, int sharers, double* ms_download) {
+    SRT_HIPCHK(hipStreamSynchronize(st));
     const double t0 = host_ms();
-    const size_t w4 = (size_t)nsub * sizeof(uint32_t), w8 = (size_t)nsub * sizeof(double);
-    int rc = table_download(lat_q, w4, slat, w4, w4, nsub, st, 1);
-    if (!rc) rc = table_download(rel, w8, srel, w8, w8, nsub, st, 1);
-    if (!rc && sms) rc = table_download(lat_ms, w8, sms, w8, w8, nsub, st, 1);
-    local->ms_download = host_ms() - t0;
+    const size_t w4 = (size_t)ncols * sizeof(uint32_t), w8 = (size_t)ncols * sizeof(double);
+    int rc = table_download(lat_q, w4, dlat, (size_t)ld * sizeof(uint32_t), w4, rows, st, sharers);
+    if (!rc) rc = table_download(rel, w8, drel, (size_t)ld * sizeof(double), w8, rows, st, sharers);
+    if (!rc && dms)
+        rc = table_download(lat_ms, w8, dms, (size_t)ld * sizeof(double), w8, rows, st, sharers);
+    *ms_download = host_ms() - t0;
+    return rc;
+}
+
+/* cnt rows of the sub-table out of full-width device rows (stride ld; dms optional): the rows
+ * `rows` of them (NULL: the first cnt) at the columns `cols` (nsub vertices), gathered into
+ * tables of their own (from B), their minimum into dmin, then into the host rows given */
+static int sub_table_out(dbufs* B, int cnt, int nsub, const int32_t* rows, const int32_t* cols,
+                         const uint32_t* dlat, const double* drel, const double* dms, int ld,
+                         uint32_t* dmin, uint32_t* lat_q, double* rel, double* lat_ms,
+                         hipStream_t st, int sharers, double* ms_download) {
+    const size_t all = (size_t)cnt * nsub;
+    uint32_t* sl;
+    double *sr, *sm = NULL;
+    int rc = SRT_OK;
+    TRY(dalloc(B, (void**)&sl, all * sizeof(uint32_t)));
+    TRY(dalloc(B, (void**)&sr, all * sizeof(double)));
+    TRY(srt_gather_sub_u32(cnt, nsub, rows, cols, dlat, ld, sl, nsub, st));
+    TRY(srt_gather_sub_f64(cnt, nsub, rows, cols, drel, ld, sr, nsub, st));
+    if (dms) {
+        TRY(dalloc(B, (void**)&sm, all * sizeof(double)));
+        TRY(srt_gather_sub_f64(cnt, nsub, rows, cols, dms, ld, sm, nsub, st));
+    }
+    TRY(srt_table_min(cnt, nsub, sl, nsub, dmin, st));
+    TRY(download_tables(cnt, nsub, nsub, sl, sr, sm, lat_q, rel, lat_ms, st, sharers, ms_download));
+out:
+    return rc;
+}
+
+/* Slots [s0, s1) of the sub-table by the sparse rows, into slat / srel / sms (optional; row
+ * stride nsub, slot s0 at their first row), their minimum into dmin. With a subset (the device
+ * list dverts) the full-width rows of a chunk of sources at a time (rows from B, sized by what is
+ * free for each of `sharers` ranks) are gathered into the sub-table; without one, the rows are
+ * the sub-table's own. acc: the first chunk's statistics, the later chunks' added. */
+static int sparse_subset_rows(const srt_sparse_graph* sg, dbufs* B, int nsub, const int32_t* dverts,
+                              int s0, int s1, int sharers, uint32_t* slat, double* srel,
+                              double* sms, uint32_t* dmin, hipStream_t st, srt_build_stats* acc) {
+    const int n = sg->n, count_ties = acc->count_ties;
+    uint32_t* dlat = NULL;
+    double *drel = NULL, *dms = NULL;
+    int chunk = s1 - s0;
+    int rc = SRT_OK;
+    if (dverts) {
+        const size_t per_row = (size_t)n * (sizeof(uint32_t) + sizeof(double) + (sms ? sizeof(double) : 0));
+        chunk = chunk_rows(0, sharers, per_row, s1 - s0);
+        TRY(dalloc(B, (void**)&dlat, (size_t)chunk * n * sizeof(uint32_t)));
+        TRY(dalloc(B, (void**)&drel, (size_t)chunk * n * sizeof(double)));
+        if (sms) TRY(dalloc(B, (void**)&dms, (size_t)chunk * n * sizeof(double)));
+    }
+    note_row_chunks(srt_ceil_div(s1 - s0, chunk));
+    for (int r0 = s0; r0 < s1; r0 += chunk) {
+        const int cnt = r0 + chunk < s1 ? chunk : s1 - r0;
+        const size_t o = (size_t)(r0 - s0) * nsub;
+        srt_build_stats cs;
+        memset(&cs, 0, sizeof(cs));
+        cs.count_ties = count_ties;
+        if (dverts) {
+            TRY(sparse_chunk(sg, dverts, r0, cnt, dlat, drel, dms, st, &cs));
+            TRY(srt_gather_sub_u32(cnt, nsub, NULL, dverts, dlat, n, slat + o, nsub, st));
+            TRY(srt_gather_sub_f64(cnt, nsub, NULL, dverts, drel, n, srel + o, nsub, st));
+            if (dms) TRY(srt_gather_sub_f64(cnt, nsub, NULL, dverts, dms, n, sms + o, nsub, st));
+        } else {
+            TRY(sparse_chunk(sg, NULL, r0, cnt, slat + o, srel + o, sms ? sms + o : NULL, st, &cs));
+        }
+        merge_stats(acc, &cs, r0 == s0);
+    }
+    TRY(srt_table_min(s1 - s0, nsub, slat, nsub, dmin, st));
+out:
     return rc;
 }
 
@@ -1535,8 +1644,6 @@ static int build_one(const srt_canon* c, const srt_build_opts* opts, int algo, i
     hipStream_t st = NULL;
     int32_t* dverts = NULL;
     uint32_t* dmin = NULL;
-    uint32_t *slat = NULL, *dlat = NULL;
-    double *srel = NULL, *sms = NULL, *drel = NULL, *dms = NULL;
     const size_t ns2 = (size_t)nsub * nsub;
     int rc = SRT_OK;
     TRYHIP(hipSetDevice(opts ? opts->device : 0));
@@ -1548,12 +1655,7 @@ static int build_one(const srt_canon* c, const srt_build_opts* opts, int algo, i
         TRYHIP(hipMemcpyAsync(dverts, verts, (size_t)nsub * sizeof(int32_t), hipMemcpyHostToDevice, st));
     }
     if (!use_sp || algo == SRT_ALGO_DENSE_FW) {
-        if (n > SRT_DENSE_MAX_N) {
-            srt_set_error("dense build supports n <= %d (n = %d); use the sparse SSSP",
-                          SRT_DENSE_MAX_N, n);
-            rc = SRT_E_RANGE;
-            goto out;
-        }
+        TRY(check_dense_n(n));
         const int ld = srt_ceil_div(n, 128) * 128; /* the u16 FW tiles need ld % 128 == 0 */
         const size_t ll = (size_t)ld * ld;
         uint32_t* dw;
@@ -1577,115 +1679,60 @@ static int build_one(const srt_canon* c, const srt_build_opts* opts, int algo, i
             if (lat_ms) TRY(dalloc(&B, (void**)&rm, (size_t)nsub * ld * sizeof(double)));
             TRY(srt_dense_rows_build_device(n, ld, nsub, dverts, dw, dr, rl, rr, rm, q, c->directed,
                                             st, &local, &rows_used));
-            if (rows_used) {
-                TRY(dalloc(&B, (void**)&slat, ns2 * sizeof(uint32_t)));
-                TRY(dalloc(&B, (void**)&srel, ns2 * sizeof(double)));
-                TRY(srt_gather_sub_u32(nsub, nsub, NULL, dverts, rl, ld, slat, nsub, st));
-                TRY(srt_gather_sub_f64(nsub, nsub, NULL, dverts, rr, ld, srel, nsub, st));
-                if (rm) {
-                    TRY(dalloc(&B, (void**)&sms, ns2 * sizeof(double)));
-                    TRY(srt_gather_sub_f64(nsub, nsub, NULL, dverts, rm, ld, sms, nsub, st));
-                }
-                TRY(srt_table_min(nsub, nsub, slat, nsub, dmin, st));
-                TRY(download_sub(nsub, slat, srel, sms, lat_q, rel, lat_ms, st, &local));
-                TRYHIP(hipMemcpyAsync(min_q, dmin, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-                TRYHIP(hipStreamSynchronize(st));
-            }
+            if (rows_used)
+                TRY(sub_table_out(&B, nsub, nsub, NULL, dverts, rl, rr, rm, ld, dmin, lat_q, rel,
+                                  lat_ms, st, 1, &local.ms_download));
         }
         if (!rows_used) {
+            uint32_t* dlat;
+            double *drel, *dms = NULL;
             TRY(dalloc(&B, (void**)&dlat, ll * sizeof(uint32_t)));
             TRY(dalloc(&B, (void**)&drel, ll * sizeof(double)));
             if (lat_ms) TRY(dalloc(&B, (void**)&dms, ll * sizeof(double)));
-        }
-        if (rows_used) {
-            /* done: the attached rows */
-        } else if (use_sp) {
-            TRY(srt_dense_build_device_ms(n, ld, c->directed, dw, dr, dlat, drel, dms, q, st,
-                                          opts ? opts->fw_block : 0, &local));
-        } else {
-            /* direct mode (topology.c:1816-1858): the (complete) graph's own edges, the self-loop
-             * on the diagonal */
-            TRYHIP(hipMemcpyAsync(dlat, dw, ll * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-            TRYHIP(hipMemcpyAsync(drel, dr, ll * sizeof(double), hipMemcpyDeviceToDevice, st));
-            if (dms) TRY(srt_quanta_to_ms(n, n, dw, ld, q, dms, ld, st));
-            local.algo = SRT_ALGO_DENSE_FW;
-        }
-        if (rows_used) {
-        } else if (verts) {
-            TRY(dalloc(&B, (void**)&slat, ns2 * sizeof(uint32_t)));
-            TRY(dalloc(&B, (void**)&srel, ns2 * sizeof(double)));
-            TRY(srt_gather_sub_u32(nsub, nsub, dverts, dverts, dlat, ld, slat, nsub, st));
-            TRY(srt_gather_sub_f64(nsub, nsub, dverts, dverts, drel, ld, srel, nsub, st));
-            if (dms) {
-                TRY(dalloc(&B, (void**)&sms, ns2 * sizeof(double)));
-                TRY(srt_gather_sub_f64(nsub, nsub, dverts, dverts, dms, ld, sms, nsub, st));
+            if (use_sp) {
+                TRY(srt_dense_build_device_ms(n, ld, c->directed, dw, dr, dlat, drel, dms, q, st,
+                                              opts ? opts->fw_block : 0, &local));
+            } else {
+                /* direct mode (topology.c:1816-1858): the (complete) graph's own edges, the
+                 * self-loop on the diagonal */
+                TRYHIP(hipMemcpyAsync(dlat, dw, ll * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+                TRYHIP(hipMemcpyAsync(drel, dr, ll * sizeof(double), hipMemcpyDeviceToDevice, st));
+                if (dms) TRY(srt_quanta_to_ms(n, n, dw, ld, q, dms, ld, st));
+                local.algo = SRT_ALGO_DENSE_FW;
             }
-            TRY(srt_table_min(nsub, nsub, slat, nsub, dmin, st));
-            TRY(download_sub(nsub, slat, srel, sms, lat_q, rel, lat_ms, st, &local));
-        } else {
-            TRY(srt_table_min(n, n, dlat, ld, dmin, st));
-            TRYHIP(hipStreamSynchronize(st)); /* the transfer alone is timed */
-            const double t0 = host_ms();
-            TRY(table_download(lat_q, (size_t)n * sizeof(uint32_t), dlat, (size_t)ld * sizeof(uint32_t),
-                               (size_t)n * sizeof(uint32_t), n, st, 1));
-            TRY(table_download(rel, (size_t)n * sizeof(double), drel, (size_t)ld * sizeof(double),
-                               (size_t)n * sizeof(double), n, st, 1));
-            if (dms)
-                TRY(table_download(lat_ms, (size_t)n * sizeof(double), dms, (size_t)ld * sizeof(double),
-                                   (size_t)n * sizeof(double), n, st, 1));
-            local.ms_download = host_ms() - t0;
-        }
-        if (!rows_used) {
-            TRYHIP(hipMemcpyAsync(min_q, dmin, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            TRYHIP(hipStreamSynchronize(st));
-        }
-        if (!use_sp) {
-            for (size_t i = 0; i < ns2; i++)
-                if (lat_q[i] >= SRT_INF) {
-                    srt_set_error("use_shortest_path=false requires a complete graph");
-                    rc = SRT_E_INVALID;
-                    goto out;
-                }
+            if (verts) {
+                TRY(sub_table_out(&B, nsub, nsub, dverts, dverts, dlat, drel, dms, ld, dmin, lat_q,
+                                  rel, lat_ms, st, 1, &local.ms_download));
+            } else {
+                TRY(srt_table_min(n, n, dlat, ld, dmin, st));
+                TRY(download_tables(n, n, ld, dlat, drel, dms, lat_q, rel, lat_ms, st, 1,
+                                    &local.ms_download));
+            }
         }
     } else {
+        /* the sub-table (every source row of the subset, its columns) on the device */
         srt_sparse_graph* sg = NULL;
+        uint32_t* slat;
+        double *srel, *sms = NULL;
         TRY(sparse_graph_from_canon(c, opts ? opts->device : 0, &sg));
-        /* the sub-table (every source row of the subset, its columns) on the device; the
-         * full-width rows of a chunk of sources are gathered into it */
-        const size_t per_row = (size_t)n * (sizeof(uint32_t) + sizeof(double) + (lat_ms ? sizeof(double) : 0));
         rc = dalloc(&B, (void**)&slat, ns2 * sizeof(uint32_t));
         if (!rc) rc = dalloc(&B, (void**)&srel, ns2 * sizeof(double));
         if (!rc && lat_ms) rc = dalloc(&B, (void**)&sms, ns2 * sizeof(double));
-        int chunk = nsub;
-        if (!rc && verts) {
-            const size_t cb = chunk_budget(0, 1) / per_row;
-            chunk = (int)(cb < (size_t)nsub ? (cb > 0 ? cb : 1) : (size_t)nsub);
-            rc = dalloc(&B, (void**)&dlat, (size_t)chunk * n * sizeof(uint32_t));
-            if (!rc) rc = dalloc(&B, (void**)&drel, (size_t)chunk * n * sizeof(double));
-            if (!rc && lat_ms) rc = dalloc(&B, (void**)&dms, (size_t)chunk * n * sizeof(double));
-        }
-        for (int r0 = 0; r0 < nsub && !rc; r0 += chunk) {
-            const int r1 = r0 + chunk < nsub ? r0 + chunk : nsub;
-            srt_build_stats cs;
-            memset(&cs, 0, sizeof(cs));
-            cs.count_ties = local.count_ties;
-            if (verts) {
-                rc = sparse_rows(sg, 0, r1 - r0, dverts + r0, dlat, drel, dms, st, &cs);
-                if (!rc) rc = srt_gather_sub_u32(r1 - r0, nsub, NULL, dverts, dlat, n, slat + (size_t)r0 * nsub, nsub, st);
-                if (!rc) rc = srt_gather_sub_f64(r1 - r0, nsub, NULL, dverts, drel, n, srel + (size_t)r0 * nsub, nsub, st);
-                if (!rc && dms) rc = srt_gather_sub_f64(r1 - r0, nsub, NULL, dverts, dms, n, sms + (size_t)r0 * nsub, nsub, st);
-            } else {
-                rc = sparse_rows(sg, r0, r1, NULL, slat + (size_t)r0 * n, srel + (size_t)r0 * n,
-                                 sms ? sms + (size_t)r0 * n : NULL, st, &cs);
-            }
-            merge_stats(&local, &cs, r0 == 0);
-        }
-        if (!rc) rc = srt_table_min(nsub, nsub, slat, nsub, dmin, st);
+        if (!rc) rc = sparse_subset_rows(sg, &B, nsub, dverts, 0, nsub, 1, slat, srel, sms, dmin, st, &local);
         srt_sparse_graph_free(sg);
         if (rc) goto out;
-        TRY(download_sub(nsub, slat, srel, sms, lat_q, rel, lat_ms, st, &local));
-        TRYHIP(hipMemcpyAsync(min_q, dmin, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        TRYHIP(hipStreamSynchronize(st));
+        TRY(download_tables(nsub, nsub, nsub, slat, srel, sms, lat_q, rel, lat_ms, st, 1,
+                            &local.ms_download));
+    }
+    TRYHIP(hipMemcpyAsync(min_q, dmin, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    TRYHIP(hipStreamSynchronize(st));
+    if (!use_sp) {
+        for (size_t i = 0; i < ns2; i++)
+            if (lat_q[i] >= SRT_INF) {
+                srt_set_error("use_shortest_path=false requires a complete graph");
+                rc = SRT_E_INVALID;
+                goto out;
+            }
     }
     if (stats) *stats = local;
 out:
@@ -1812,8 +1859,6 @@ static void* mjob_dense(void* p) {
             }
             for (int i = 0; i < cnt; i++) hrows[i] = j->verts[i0 + i] - b;
             int32_t *drows, *dcols;
-            uint32_t* sl;
-            double *sr, *sm = NULL;
             rc = dalloc(&B, (void**)&drows, (size_t)cnt * sizeof(int32_t));
             if (!rc) rc = dalloc(&B, (void**)&dcols, (size_t)nsub * sizeof(int32_t));
             if (!rc && hipMemcpyAsync(drows, hrows, (size_t)cnt * sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess)
@@ -1823,33 +1868,15 @@ static void* mjob_dense(void* p) {
             if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = SRT_E_DEVICE;
             free(hrows);
             if (rc) goto out;
-            TRY(dalloc(&B, (void**)&sl, (size_t)cnt * nsub * sizeof(uint32_t)));
-            TRY(dalloc(&B, (void**)&sr, (size_t)cnt * nsub * sizeof(double)));
-            TRY(srt_gather_sub_u32(cnt, nsub, drows, dcols, dlat, j->ld, sl, nsub, st));
-            TRY(srt_gather_sub_f64(cnt, nsub, drows, dcols, drel, j->ld, sr, nsub, st));
-            if (dms) {
-                TRY(dalloc(&B, (void**)&sm, (size_t)cnt * nsub * sizeof(double)));
-                TRY(srt_gather_sub_f64(cnt, nsub, drows, dcols, dms, j->ld, sm, nsub, st));
-            }
-            TRY(srt_table_min(cnt, nsub, sl, nsub, dmin, st));
-            const double t0 = host_ms();
-            const size_t w4 = (size_t)nsub * sizeof(uint32_t), w8 = (size_t)nsub * sizeof(double);
-            TRY(table_download(j->lat_q + (size_t)i0 * nsub, w4, sl, w4, w4, cnt, st, j->R));
-            TRY(table_download(j->rel + (size_t)i0 * nsub, w8, sr, w8, w8, cnt, st, j->R));
-            if (sm) TRY(table_download(j->lat_ms + (size_t)i0 * nsub, w8, sm, w8, w8, cnt, st, j->R));
-            j->st.ms_download = host_ms() - t0;
+            TRY(sub_table_out(&B, cnt, nsub, drows, dcols, dlat, drel, dms, j->ld, dmin,
+                              j->lat_q + (size_t)i0 * nsub, j->rel + (size_t)i0 * nsub,
+                              dms ? j->lat_ms + (size_t)i0 * nsub : NULL, st, j->R,
+                              &j->st.ms_download));
         } else if (cnt > 0) {
             TRY(srt_table_min(cnt, n, dlat, j->ld, dmin, st));
-            const double t0 = host_ms();
-            const size_t w4 = (size_t)n * sizeof(uint32_t), w8 = (size_t)n * sizeof(double);
-            TRY(table_download(j->lat_q + (size_t)i0 * n, w4, dlat, (size_t)j->ld * sizeof(uint32_t), w4,
-                               cnt, st, j->R));
-            TRY(table_download(j->rel + (size_t)i0 * n, w8, drel, (size_t)j->ld * sizeof(double), w8, cnt,
-                               st, j->R));
-            if (dms)
-                TRY(table_download(j->lat_ms + (size_t)i0 * n, w8, dms, (size_t)j->ld * sizeof(double), w8,
-                                   cnt, st, j->R));
-            j->st.ms_download = host_ms() - t0;
+            TRY(download_tables(cnt, n, j->ld, dlat, drel, dms, j->lat_q + (size_t)i0 * n,
+                                j->rel + (size_t)i0 * n, dms ? j->lat_ms + (size_t)i0 * n : NULL, st,
+                                j->R, &j->st.ms_download));
         }
         TRYHIP(hipMemcpyAsync(&j->min_q, dmin, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         TRYHIP(hipStreamSynchronize(st));
@@ -1869,16 +1896,15 @@ static void* mjob_sparse(void* p) {
     B.k = 0;
     hipStream_t st = NULL;
     srt_sparse_graph* sg = NULL;
-    const int n = j->n, nsub = j->nsub, per = srt_ceil_div(nsub, j->R);
+    const int nsub = j->nsub, per = srt_ceil_div(nsub, j->R);
     const int s0 = j->rank * per < nsub ? j->rank * per : nsub;
     const int s1 = (s0 + per < nsub) ? s0 + per : nsub;
     /* this rank's source rows only: every row is its own source's (no mirror), and the host
      * table the ranks of this process share receives each shard directly */
     const size_t all = (size_t)(s1 > s0 ? s1 - s0 : 1) * nsub;
-    uint32_t *slat, *dlat = NULL, *dmin;
-    double *srel, *sms = NULL, *drel = NULL, *dms = NULL;
+    uint32_t *slat, *dmin;
+    double *srel, *sms = NULL;
     int32_t* dverts = NULL;
-    int chunk = s1 - s0;
     srt_set_virtual_slot(j->virt ? j->rank : -1);
     TRYHIP(hipSetDevice(j->dev));
     TRYHIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
@@ -1889,34 +1915,12 @@ static void* mjob_sparse(void* p) {
     if (j->lat_ms) TRY(dalloc(&B, (void**)&sms, all * sizeof(double)));
     TRYHIP(hipMemsetAsync(dmin, 0xFF, sizeof(uint32_t), st));
     if (j->verts && s1 > s0) {
-        const size_t per_row = (size_t)n * (sizeof(uint32_t) + sizeof(double) + (sms ? sizeof(double) : 0));
-        const size_t cb = chunk_budget(0, j->virt ? j->R : 1) / per_row;
-        chunk = (int)(cb < (size_t)(s1 - s0) ? (cb > 0 ? cb : 1) : (size_t)(s1 - s0));
         TRY(dalloc(&B, (void**)&dverts, (size_t)nsub * sizeof(int32_t)));
         TRYHIP(hipMemcpyAsync(dverts, j->verts, (size_t)nsub * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        TRY(dalloc(&B, (void**)&dlat, (size_t)chunk * n * sizeof(uint32_t)));
-        TRY(dalloc(&B, (void**)&drel, (size_t)chunk * n * sizeof(double)));
-        if (sms) TRY(dalloc(&B, (void**)&dms, (size_t)chunk * n * sizeof(double)));
-    }
-    for (int r0 = s0; r0 < s1; r0 += chunk) {
-        const int r1 = r0 + chunk < s1 ? r0 + chunk : s1;
-        srt_build_stats cs;
-        memset(&cs, 0, sizeof(cs));
-        cs.count_ties = j->st.count_ties;
-        if (j->verts) {
-            const size_t o = (size_t)(r0 - s0) * nsub;
-            TRY(sparse_rows(sg, 0, r1 - r0, dverts + r0, dlat, drel, dms, st, &cs));
-            TRY(srt_gather_sub_u32(r1 - r0, nsub, NULL, dverts, dlat, n, slat + o, nsub, st));
-            TRY(srt_gather_sub_f64(r1 - r0, nsub, NULL, dverts, drel, n, srel + o, nsub, st));
-            if (dms) TRY(srt_gather_sub_f64(r1 - r0, nsub, NULL, dverts, dms, n, sms + o, nsub, st));
-        } else {
-            const size_t o = (size_t)(r0 - s0) * n;
-            TRY(sparse_rows(sg, r0, r1, NULL, slat + o, srel + o, sms ? sms + o : NULL, st, &cs));
-        }
-        merge_stats(&j->st, &cs, r0 == s0);
     }
     if (s1 > s0) {
-        TRY(srt_table_min(s1 - s0, nsub, slat, nsub, dmin, st));
+        TRY(sparse_subset_rows(sg, &B, nsub, dverts, s0, s1, j->virt ? j->R : 1, slat, srel, sms,
+                               dmin, st, &j->st));
         TRYHIP(hipMemcpyAsync(j->lat_q + (size_t)s0 * nsub, slat,
                               (size_t)(s1 - s0) * nsub * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         TRYHIP(hipMemcpyAsync(j->rel + (size_t)s0 * nsub, srel,
@@ -1954,14 +1958,7 @@ static int build_multi(const srt_canon* c, const srt_build_opts* opts, int algo,
         rc = SRT_E_NOMEM;
         goto done;
     }
-    if (algo == SRT_ALGO_DENSE_FW) {
-        if (n > SRT_DENSE_MAX_N) {
-            srt_set_error("dense build supports n <= %d (n = %d); use the sparse SSSP",
-                          SRT_DENSE_MAX_N, n);
-            rc = SRT_E_RANGE;
-            goto done;
-        }
-    }
+    if (algo == SRT_ALGO_DENSE_FW && (rc = check_dense_n(n))) goto done;
     for (int i = 0; i < R; i++) devs[i] = virt ? 0 : i;
     if ((rc = virt ? srt_comm_init_virtual(R, 0, comms) : srt_comm_init_all(R, devs, comms)))
         goto done;
@@ -2042,6 +2039,44 @@ static int virtual_ranks_env(void) {
     return v > 0 ? (v < 64 ? v : 64) : 0;
 }
 
+/* The front end of every build from host edges: the canonical form of g, the algorithm, then
+ * body(c, algo, ms_canon), whose return code is the build's.
+ * A dense-shaped graph (by its edge count, an upper bound on its arcs) goes to the device as its
+ * edge list; every other graph, and one the edge form refuses, through the host canonical CSR
+ * (graph.c). The dense auto choice is confirmed on the exact arcs by the scatter: a body that
+ * returns SRT_FALLBACK_CANON is run once more, on the host CSR.
+ * A wide graph (distances may pass u32 quanta) goes to the sparse rows unless dense is forced;
+ * whether it can be built at all is the body's to say. use_sp == 0: the direct (dense) build. */
+template <class Body>
+static int with_canon(const srt_edges* g, const srt_build_opts* opts, int use_sp, Body body) {
+    const int forced = opts ? opts->algo : SRT_ALGO_AUTO;
+    int edge_form = 0;
+    if (forced != SRT_ALGO_SPARSE_SSSP && g->n <= SRT_DENSE_MAX_N && g->m > 0) {
+        const double n = g->n, ub = (double)g->m * (g->directed ? 1 : 2);
+        edge_form = g->n <= 2048 || ub * 16.0 >= n * n || forced == SRT_ALGO_DENSE_FW || !use_sp;
+    }
+    int rc = SRT_OK;
+    for (int attempt = 0; attempt < 2; attempt++) {
+        srt_canon c;
+        const double t0 = host_ms();
+        if (edge_form && attempt == 0 && canon_from_edges(g, &c) == 0) {
+            c.verify_dense = use_sp && forced != SRT_ALGO_DENSE_FW;
+        } else {
+            rc = srt_canon_build(g, &c);
+            if (rc) return rc;
+        }
+        const double ms_canon = host_ms() - t0;
+        const int algo = !use_sp ? SRT_ALGO_DENSE_FW
+                         : c.wide && forced != SRT_ALGO_DENSE_FW ? SRT_ALGO_SPARSE_SSSP
+                                                                 : choose_algo(&c, opts);
+        rc = body((const srt_canon*)&c, algo, ms_canon);
+        srt_canon_free(&c);
+        if (rc != SRT_FALLBACK_CANON) break;
+        srt_log(SRT_LOG_INFO, "edge-list dense build: too few distinct arcs, the host canonical form decides");
+    }
+    return rc;
+}
+
 static int build_tables_subset_impl(const srt_edges* g, const srt_build_opts* opts, int32_t ngpus,
                                     int virt, int32_t nsub, const int32_t* verts, uint32_t* lat_q,
                                     uint64_t* quantum_ns, double* rel, double* lat_ms,
@@ -2055,59 +2090,34 @@ static int build_tables_subset_impl(const srt_edges* g, const srt_build_opts* op
                       "indices (or NULL with nsub = n)");
         return SRT_E_ARG;
     }
+    last_row_chunks.store(0, std::memory_order_relaxed);
     const int avail = srt_device_count();
     if (avail < 1) {
         srt_set_error("srt_build_tables: no HIP device");
         return SRT_E_DEVICE;
     }
     const int use_sp = opts ? opts->use_shortest_path : 1;
-    const int forced = opts ? opts->algo : SRT_ALGO_AUTO;
-    /* a dense-shaped graph (by its edge count, an upper bound on its arcs) goes to the device as
-     * its edge list; every other graph, and one the edge form refuses, through the host canonical
-     * CSR (graph.c). The dense auto choice is confirmed on the exact arcs by a one-rank scatter. */
-    int edge_form = 0;
-    if (forced != SRT_ALGO_SPARSE_SSSP && g->n <= SRT_DENSE_MAX_N && g->m > 0) {
-        const double n = g->n, ub = (double)g->m * (g->directed ? 1 : 2);
-        edge_form = g->n <= 2048 || ub * 16.0 >= n * n || forced == SRT_ALGO_DENSE_FW || !use_sp;
-    }
-    int rc = SRT_OK;
-    for (int attempt = 0; attempt < 2; attempt++) {
-        srt_canon c;
-        const double t0 = host_ms();
-        if (edge_form && attempt == 0 && canon_from_edges(g, &c) == 0) {
-            c.verify_dense = use_sp && forced != SRT_ALGO_DENSE_FW;
-        } else {
-            if (attempt == 0) edge_form = 0;
-            rc = srt_canon_build(g, &c);
-            if (rc) return rc;
-        }
-        const double ms_canon = host_ms() - t0;
-        *quantum_ns = c.quantum_ns;
-        const int algo = use_sp ? (c.wide && forced != SRT_ALGO_DENSE_FW ? SRT_ALGO_SPARSE_SSSP
-                                                                          : choose_algo(&c, opts))
-                                : SRT_ALGO_DENSE_FW;
-        if (use_sp && c.wide && (algo == SRT_ALGO_DENSE_FW || !lat_ms)) {
+    return with_canon(g, opts, use_sp, [&](const srt_canon* c, int algo, double ms_canon) {
+        *quantum_ns = c->quantum_ns;
+        /* a wide graph is built by the sparse u64 rows alone, into the f64 ms table */
+        if (use_sp && c->wide && (algo == SRT_ALGO_DENSE_FW || !lat_ms)) {
             srt_set_error("shortest-path latencies may pass the u32 range (bound %llu quanta of %llu "
                           "ns): only the sparse u64 rows build this graph, and its latencies are "
                           "served from the f64 ms table (%s)",
-                          (unsigned long long)c.dist_bound, (unsigned long long)c.quantum_ns,
+                          (unsigned long long)c->dist_bound, (unsigned long long)c->quantum_ns,
                           algo == SRT_ALGO_DENSE_FW ? "dense requested" : "no lat_ms output");
-            srt_canon_free(&c);
-            return SRT_E_RANGE;
+            return (int)SRT_E_RANGE;
         }
         const int R = virt ? virt : (ngpus < avail ? ngpus : avail);
         uint32_t mq = 0xFFFFFFFFu;
-        if (R > 1 && use_sp)
-            rc = build_multi(&c, opts, algo, R, virt, nsub, verts, lat_q, rel, lat_ms, &mq, stats);
-        else
-            rc = build_one(&c, opts, algo, nsub, verts, lat_q, rel, lat_ms, &mq, stats);
+        const int rc = R > 1 && use_sp ? build_multi(c, opts, algo, R, virt, nsub, verts, lat_q, rel,
+                                                     lat_ms, &mq, stats)
+                                       : build_one(c, opts, algo, nsub, verts, lat_q, rel, lat_ms,
+                                                   &mq, stats);
         if (!rc && min_lat_q) *min_lat_q = mq;
         if (!rc && stats) stats->ms_canon = ms_canon;
-        srt_canon_free(&c);
-        if (rc != SRT_FALLBACK_CANON) break;
-        srt_log(SRT_LOG_INFO, "edge-list dense build: too few distinct arcs, the host canonical form decides");
-    }
-    return rc;
+        return rc;
+    });
 }
 
 /* SRT_VIRTUAL_RANKS applies only to a multi-GPU request (ngpus > 1): a variable left set must not
@@ -2141,6 +2151,7 @@ extern "C" int srt_build_tables_multi(const srt_edges* g, const srt_build_opts* 
     const int avail = srt_device_count();
     const int virt = virtual_ranks_env();
     if (ngpus == 1 && !virt && avail >= 1) {
+        last_row_chunks.store(0, std::memory_order_relaxed);
         srt_canon c;
         int rc = srt_canon_build(g, &c);
         if (rc) return rc;
@@ -2187,94 +2198,154 @@ extern "C" int srt_routes_rows_device(const srt_sparse_graph* g, int32_t nsrc, c
     return rc;
 }
 
-/* one GPU: rows of the sources verts (NULL: every vertex) into the host outputs, in chunks */
-static int routes_one(const srt_canon* c, const srt_build_opts* opts, int algo, int nsub,
-                      const int32_t* verts, int32_t* const hout[3], srt_route_stats* stats) {
+/* The route rows of the sources verts (NULL: every vertex) on one GPU, a chunk at a time, for the
+ * route export and the link load. route_source_open puts the distances' origin on the device (the
+ * dense tables and their essential in-lists, or the sparse graph); route_source_chunks sizes the
+ * chunk from the memory free at that point and allocates its rows; route_source_step computes the
+ * rows of one chunk; route_source_close releases everything (after a failed open too). Start from
+ * a zeroed struct. */
+struct route_source {
+    int n, nsub, dense, ld;
+    hipStream_t st;
+    dbufs B;
+    int32_t* dverts;
+    srt_sparse_graph* sg; /* sparse */
+    uint32_t* dlat;       /* dense: the ld x ld table; sparse: the chunk's distance rows */
+    double* drel;
+    int32_t *ess_rp, *ess_col; /* dense: the essential in-lists (srt_routes_ess_build) */
+    uint32_t* ess_w;
+    /* the in-arc CSR the route pass reads and the load is indexed by; sorted: its lists ascend */
+    const int32_t *irp, *icol;
+    const uint32_t* iw;
+    int64_t narcs;
+    int sorted;
+    int chunk;        /* rows a step */
+    int32_t* dout[3]; /* pred, first, hops of the last step's rows (stride n; NULL: not asked) */
+    int cnt;          /* ... how many, and their sources (NULL: the vertices from the step's r0) */
+    const int32_t* srcs;
+    srt_route_stats stats; /* ms_tables, ms_routes, ess_arcs, max_hops, stage_forms so far */
+};
+
+static int route_source_open(route_source* s, const srt_canon* c, const srt_build_opts* opts,
+                             int algo, int nsub, const int32_t* verts) {
     const int n = c->n;
     const int dev = opts ? opts->device : 0;
-    srt_route_stats local;
-    memset(&local, 0, sizeof(local));
     srt_build_stats bs;
     memset(&bs, 0, sizeof(bs));
-    dbufs B;
-    B.k = 0;
-    hipStream_t st = NULL;
-    int32_t* dverts = NULL;
-    int32_t* dout[3] = {NULL, NULL, NULL};
-    uint32_t *dw = NULL, *dlat = NULL, *iw = NULL;
-    double *dr = NULL, *drel = NULL;
-    int32_t *irp = NULL, *icol = NULL;
-    srt_sparse_graph* sg = NULL;
-    const int nout = (hout[0] ? 1 : 0) + (hout[1] ? 1 : 0) + (hout[2] ? 1 : 0);
-    const bool dense = algo == SRT_ALGO_DENSE_FW;
-    const int ld = srt_ceil_div(n, 128) * 128;
-    const size_t per_row = (size_t)n * ((dense ? 0 : 12) + 4 * (size_t)(nout ? nout : 1));
-    int chunk = nsub;
+    s->n = n;
+    s->nsub = nsub;
+    s->dense = algo == SRT_ALGO_DENSE_FW;
+    s->ld = srt_ceil_div(n, 128) * 128;
     int rc = SRT_OK;
     TRYHIP(hipSetDevice(dev));
-    TRYHIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    TRYHIP(hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking));
     if (verts) {
-        TRY(dalloc(&B, (void**)&dverts, (size_t)nsub * sizeof(int32_t)));
-        TRYHIP(hipMemcpyAsync(dverts, verts, (size_t)nsub * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        TRY(dalloc(&s->B, (void**)&s->dverts, (size_t)nsub * sizeof(int32_t)));
+        TRYHIP(hipMemcpyAsync(s->dverts, verts, (size_t)nsub * sizeof(int32_t), hipMemcpyHostToDevice, s->st));
     }
-    if (dense) {
-        if (n > SRT_DENSE_MAX_N) {
-            srt_set_error("dense build supports n <= %d (n = %d); use the sparse SSSP",
-                          SRT_DENSE_MAX_N, n);
-            rc = SRT_E_RANGE;
-            goto out;
-        }
-        const size_t ll = (size_t)ld * ld;
-        TRY(dalloc(&B, (void**)&dw, ll * sizeof(uint32_t)));
-        TRY(dalloc(&B, (void**)&dr, ll * sizeof(double)));
-        TRY(dalloc(&B, (void**)&dlat, ll * sizeof(uint32_t)));
-        TRY(dalloc(&B, (void**)&drel, ll * sizeof(double)));
-        TRY(dense_upload(c, ld, 0, ld, dw, dr, st, 1));
-        TRY(srt_dense_build_device_ms(n, ld, c->directed, dw, dr, dlat, drel, NULL, c->quantum_ns, st,
-                                      opts ? opts->fw_block : 0, &bs));
-        local.ms_tables = bs.ms_total;
-        TRY(srt_routes_ess_build(n, ld, c->directed, dw, dlat, st, &irp, &icol, &iw, &local.ess_arcs,
-                                 &local.ms_routes));
+    if (s->dense) {
+        const size_t ll = (size_t)s->ld * s->ld;
+        uint32_t* dw;
+        double* dr;
+        TRY(check_dense_n(n));
+        TRY(dalloc(&s->B, (void**)&dw, ll * sizeof(uint32_t)));
+        TRY(dalloc(&s->B, (void**)&dr, ll * sizeof(double)));
+        TRY(dalloc(&s->B, (void**)&s->dlat, ll * sizeof(uint32_t)));
+        TRY(dalloc(&s->B, (void**)&s->drel, ll * sizeof(double)));
+        TRY(dense_upload(c, s->ld, 0, s->ld, dw, dr, s->st, 1));
+        TRY(srt_dense_build_device_ms(n, s->ld, c->directed, dw, dr, s->dlat, s->drel, NULL,
+                                      c->quantum_ns, s->st, opts ? opts->fw_block : 0, &bs));
+        s->stats.ms_tables = bs.ms_total;
+        TRY(srt_routes_ess_build(n, s->ld, c->directed, dw, s->dlat, s->st, &s->ess_rp, &s->ess_col,
+                                 &s->ess_w, &s->stats.ess_arcs, &s->stats.ms_routes));
+        s->irp = s->ess_rp;
+        s->icol = s->ess_col;
+        s->iw = s->ess_w;
+        s->narcs = s->stats.ess_arcs;
+        /* an undirected graph's essential lists are compacted in column order, a directed one's
+         * through per-head cursors in no order */
+        s->sorted = c->directed ? 0 : 1;
     } else {
-        TRY(sparse_graph_from_canon(c, dev, &sg));
+        TRY(sparse_graph_from_canon(c, dev, &s->sg));
+        s->irp = s->sg->irp;
+        s->icol = s->sg->icol;
+        s->iw = s->sg->iw;
+        s->narcs = s->sg->arcs;
+        s->sorted = 1;
     }
-    {
-        const size_t cb = chunk_budget(0, 1) / per_row;
-        chunk = (int)(cb < (size_t)nsub ? (cb > 0 ? cb : 1) : (size_t)nsub);
-    }
-    if (!dense) {
-        TRY(dalloc(&B, (void**)&dlat, (size_t)chunk * n * sizeof(uint32_t)));
-        TRY(dalloc(&B, (void**)&drel, (size_t)chunk * n * sizeof(double)));
+out:
+    return rc;
+}
+
+/* the chunk: what is free now beyond `reserved` bytes, over a row's bytes -- the distance and
+ * reliability rows of a sparse build, the outputs asked for (want) and the caller's row_extra */
+static int route_source_chunks(route_source* s, size_t reserved, size_t row_extra,
+                               const bool want[3]) {
+    const size_t n = (size_t)s->n;
+    const int nout = (want[0] ? 1 : 0) + (want[1] ? 1 : 0) + (want[2] ? 1 : 0);
+    int rc = SRT_OK;
+    s->chunk = chunk_rows(reserved, 1, n * ((s->dense ? 0 : 12) + 4 * (size_t)nout) + row_extra,
+                          s->nsub);
+    note_row_chunks(srt_ceil_div(s->nsub, s->chunk));
+    if (!s->dense) {
+        TRY(dalloc(&s->B, (void**)&s->dlat, (size_t)s->chunk * n * sizeof(uint32_t)));
+        TRY(dalloc(&s->B, (void**)&s->drel, (size_t)s->chunk * n * sizeof(double)));
     }
     for (int i = 0; i < 3; i++)
-        if (hout[i]) TRY(dalloc(&B, (void**)&dout[i], (size_t)chunk * n * sizeof(int32_t)));
-    for (int r0 = 0; r0 < nsub; r0 += chunk) {
-        const int cnt = r0 + chunk < nsub ? chunk : nsub - r0;
-        const int32_t* cs = verts ? dverts + r0 : NULL;
-        if (dense) {
-            TRY(srt_routes_rows_timed(n, cnt, cs, r0, 1, dlat, (size_t)ld, irp, icol, iw, dout[0],
-                                      dout[1], dout[2], (size_t)n, st, &local));
-        } else {
-            memset(&bs, 0, sizeof(bs));
-            TRY(verts ? sparse_rows(sg, 0, cnt, cs, dlat, drel, NULL, st, &bs)
-                      : sparse_rows(sg, r0, r0 + cnt, NULL, dlat, drel, NULL, st, &bs));
-            local.ms_tables += bs.ms_total;
-            TRY(srt_routes_rows_timed(n, cnt, cs, r0, 0, dlat, (size_t)n, sg->irp, sg->icol, sg->iw,
-                                      dout[0], dout[1], dout[2], (size_t)n, st, &local));
-        }
-        const size_t w4 = (size_t)n * sizeof(int32_t);
-        for (int i = 0; i < 3; i++)
-            if (hout[i]) TRY(table_download(hout[i] + (size_t)r0 * n, w4, dout[i], w4, w4, cnt, st, 1));
-    }
-    if (stats) *stats = local;
+        if (want[i]) TRY(dalloc(&s->B, (void**)&s->dout[i], (size_t)s->chunk * n * sizeof(int32_t)));
 out:
-    if (st) {
-        srt_routes_ess_free(irp, icol, iw, st);
-        (void)hipStreamSynchronize(st);
-        (void)hipStreamDestroy(st);
+    return rc;
+}
+
+/* the rows of the sources at slots [r0, r0 + chunk) (fewer at the end) into dout */
+static int route_source_step(route_source* s, int r0) {
+    const int n = s->n;
+    int rc = SRT_OK;
+    s->cnt = r0 + s->chunk < s->nsub ? s->chunk : s->nsub - r0;
+    s->srcs = s->dverts ? s->dverts + r0 : NULL;
+    if (!s->dense) { /* the dense table holds every row already */
+        srt_build_stats bs;
+        memset(&bs, 0, sizeof(bs));
+        TRY(sparse_chunk(s->sg, s->dverts, r0, s->cnt, s->dlat, s->drel, NULL, s->st, &bs));
+        s->stats.ms_tables += bs.ms_total;
     }
-    srt_sparse_graph_free(sg);
-    dfree(&B);
+    TRY(srt_routes_rows_timed(n, s->cnt, s->srcs, r0, s->dense, s->dlat,
+                              (size_t)(s->dense ? s->ld : n), s->irp, s->icol, s->iw, s->dout[0],
+                              s->dout[1], s->dout[2], (size_t)n, s->st, &s->stats));
+out:
+    return rc;
+}
+
+static void route_source_close(route_source* s) {
+    if (s->st) {
+        srt_routes_ess_free(s->ess_rp, s->ess_col, s->ess_w, s->st);
+        (void)hipStreamSynchronize(s->st);
+        (void)hipStreamDestroy(s->st);
+    }
+    srt_sparse_graph_free(s->sg);
+    dfree(&s->B);
+}
+
+/* one GPU: the route source's rows into the host outputs */
+static int routes_one(const srt_canon* c, const srt_build_opts* opts, int algo, int nsub,
+                      const int32_t* verts, int32_t* const hout[3], srt_route_stats* stats) {
+    const size_t w4 = (size_t)c->n * sizeof(int32_t);
+    const bool want[3] = {hout[0] != NULL, hout[1] != NULL, hout[2] != NULL};
+    route_source src = {};
+    int rc = SRT_OK;
+    TRY(route_source_open(&src, c, opts, algo, nsub, verts));
+    /* with no output asked, a row still counts as one */
+    TRY(route_source_chunks(&src, 0, want[0] || want[1] || want[2] ? 0 : w4, want));
+    for (int r0 = 0; r0 < nsub; r0 += src.chunk) {
+        TRY(route_source_step(&src, r0));
+        for (int i = 0; i < 3; i++)
+            if (hout[i])
+                TRY(table_download(hout[i] + (size_t)r0 * c->n, w4, src.dout[i], w4, w4, src.cnt,
+                                   src.st, 1));
+    }
+    if (stats) *stats = src.stats;
+out:
+    route_source_close(&src);
     return rc;
 }
 
@@ -2282,11 +2353,7 @@ out:
 static int routes_direct(const srt_edges* g, int32_t nsrc, const int32_t* srcs,
                          int32_t* const hout[3]) {
     const int64_t n = g->n;
-    if (n > SRT_DENSE_MAX_N) {
-        srt_set_error("dense build supports n <= %d (n = %d); use the sparse SSSP", SRT_DENSE_MAX_N,
-                      g->n);
-        return SRT_E_RANGE;
-    }
+    if (check_dense_n(g->n)) return SRT_E_RANGE;
     std::vector<uint8_t> have((size_t)((n * n + 7) / 8), 0);
     int64_t pairs = 0;
     auto mark = [&](int64_t u, int64_t v) {
@@ -2333,6 +2400,7 @@ extern "C" int srt_build_routes(const srt_edges* g, const srt_build_opts* opts, 
                       "indices (or NULL with nsrc = n)");
         return SRT_E_ARG;
     }
+    last_row_chunks.store(0, std::memory_order_relaxed);
     int32_t* const hout[3] = {pred, first_hop, hops};
     const int use_sp = opts ? opts->use_shortest_path : 1;
     if (!use_sp) {
@@ -2343,37 +2411,15 @@ extern "C" int srt_build_routes(const srt_edges* g, const srt_build_opts* opts, 
         srt_set_error("srt_build_routes: no HIP device");
         return SRT_E_DEVICE;
     }
-    /* the table build's own route to an algorithm (build_tables_subset_impl) */
-    const int forced = opts ? opts->algo : SRT_ALGO_AUTO;
-    int edge_form = 0;
-    if (forced != SRT_ALGO_SPARSE_SSSP && g->n <= SRT_DENSE_MAX_N && g->m > 0) {
-        const double n = g->n, ub = (double)g->m * (g->directed ? 1 : 2);
-        edge_form = g->n <= 2048 || ub * 16.0 >= n * n || forced == SRT_ALGO_DENSE_FW;
-    }
-    int rc = SRT_OK;
-    for (int attempt = 0; attempt < 2; attempt++) {
-        srt_canon c;
-        if (edge_form && attempt == 0 && canon_from_edges(g, &c) == 0) {
-            c.verify_dense = forced != SRT_ALGO_DENSE_FW;
-        } else {
-            if (attempt == 0) edge_form = 0;
-            rc = srt_canon_build(g, &c);
-            if (rc) return rc;
-        }
-        const int algo = c.wide && forced != SRT_ALGO_DENSE_FW ? SRT_ALGO_SPARSE_SSSP
-                                                                : choose_algo(&c, opts);
-        if (c.wide) {
+    return with_canon(g, opts, 1, [&](const srt_canon* c, int algo, double) {
+        if (c->wide) {
             srt_set_error("srt_build_routes: shortest-path latencies may pass the u32 range (bound "
                           "%llu quanta of %llu ns); the route pass reads u32 rows only",
-                          (unsigned long long)c.dist_bound, (unsigned long long)c.quantum_ns);
-            srt_canon_free(&c);
-            return SRT_E_RANGE;
+                          (unsigned long long)c->dist_bound, (unsigned long long)c->quantum_ns);
+            return (int)SRT_E_RANGE;
         }
-        rc = routes_one(&c, opts, algo, nsrc, srcs, hout, stats);
-        srt_canon_free(&c);
-        if (rc != SRT_FALLBACK_CANON) break;
-    }
-    return rc;
+        return routes_one(c, opts, algo, nsrc, srcs, hout, stats);
+    });
 }
 
 /* ------------------------------------------------------------------------------------------ */
@@ -2537,84 +2583,33 @@ static int link_load_collect(int n, const int32_t* irp, const int32_t* icol, con
     return SRT_OK;
 }
 
-/* one GPU: routes_one's loop with the load pass behind the route pass of every chunk */
+/* one GPU: the load pass behind the route pass of every chunk of the route source, over the
+ * chunk's demand rows, which are built on the device */
 static int link_load_one(const srt_canon* c, const srt_build_opts* opts, int algo,
                          const ll_demand* dm, srt_link_load* ll) {
     const int n = c->n;
     const int nsub = dm->nsub;
-    const int32_t* verts = dm->verts;
-    const int dev = opts ? opts->device : 0;
-    srt_route_stats local;
-    memset(&local, 0, sizeof(local));
-    srt_build_stats bs;
-    memset(&bs, 0, sizeof(bs));
+    route_source src = {};
     dbufs B;
     B.k = 0;
-    hipStream_t st = NULL;
-    int32_t* dverts = NULL;
-    int32_t *dpred = NULL, *dhops = NULL, *dtgt = NULL;
+    int32_t* dtgt = NULL;
     int64_t* drowptr = NULL;
     uint64_t *ddem = NULL, *dval = NULL, *dload = NULL, *dthrough = NULL, *dtot = NULL;
-    uint32_t *dw = NULL, *dlat = NULL, *iw = NULL;
-    double *dr = NULL, *drel = NULL;
-    int32_t *irp = NULL, *icol = NULL;
-    const int32_t *lirp = NULL, *licol = NULL; /* the CSR the load is indexed by */
     int64_t narcs = 0, max_ent = 0;
-    srt_sparse_graph* sg = NULL;
-    const bool dense = algo == SRT_ALGO_DENSE_FW;
-    const int ld = srt_ceil_div(n, 128) * 128;
-    /* per row: the distance and reliability rows (sparse), pred, hops and the u64 demand */
-    const size_t per_row = (size_t)n * ((dense ? 0 : 12) + 8 + 8);
-    int chunk = nsub;
     int32_t forms = 0, mh = 0;
     uint64_t htot[3] = {0, 0, 0};
+    const bool want[3] = {true, false, true}; /* pred and hops */
+    hipStream_t st = NULL;
     std::vector<int32_t> hirp, hicol;
     std::vector<uint64_t> hload;
     std::vector<int64_t> rel_rowptr;
     int rc = SRT_OK;
-    TRYHIP(hipSetDevice(dev));
-    TRYHIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    if (verts) {
-        TRY(dalloc(&B, (void**)&dverts, (size_t)nsub * sizeof(int32_t)));
-        TRYHIP(hipMemcpyAsync(dverts, verts, (size_t)nsub * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    }
-    if (dense) {
-        if (n > SRT_DENSE_MAX_N) {
-            srt_set_error("dense build supports n <= %d (n = %d); use the sparse SSSP",
-                          SRT_DENSE_MAX_N, n);
-            rc = SRT_E_RANGE;
-            goto out;
-        }
-        const size_t ll2 = (size_t)ld * ld;
-        TRY(dalloc(&B, (void**)&dw, ll2 * sizeof(uint32_t)));
-        TRY(dalloc(&B, (void**)&dr, ll2 * sizeof(double)));
-        TRY(dalloc(&B, (void**)&dlat, ll2 * sizeof(uint32_t)));
-        TRY(dalloc(&B, (void**)&drel, ll2 * sizeof(double)));
-        TRY(dense_upload(c, ld, 0, ld, dw, dr, st, 1));
-        TRY(srt_dense_build_device_ms(n, ld, c->directed, dw, dr, dlat, drel, NULL, c->quantum_ns, st,
-                                      opts ? opts->fw_block : 0, &bs));
-        local.ms_tables = bs.ms_total;
-        TRY(srt_routes_ess_build(n, ld, c->directed, dw, dlat, st, &irp, &icol, &iw, &narcs,
-                                 &local.ms_routes));
-        lirp = irp;
-        licol = icol;
-    } else {
-        TRY(sparse_graph_from_canon(c, dev, &sg));
-        lirp = sg->irp;
-        licol = sg->icol;
-        narcs = sg->arcs;
-    }
-    {
-        const size_t cb = chunk_budget((size_t)narcs * 8, 1) / per_row;
-        chunk = (int)(cb < (size_t)nsub ? (cb > 0 ? cb : 1) : (size_t)nsub);
-    }
-    if (!dense) {
-        TRY(dalloc(&B, (void**)&dlat, (size_t)chunk * n * sizeof(uint32_t)));
-        TRY(dalloc(&B, (void**)&drel, (size_t)chunk * n * sizeof(double)));
-    }
-    TRY(dalloc(&B, (void**)&dpred, (size_t)chunk * n * sizeof(int32_t)));
-    TRY(dalloc(&B, (void**)&dhops, (size_t)chunk * n * sizeof(int32_t)));
-    TRY(dalloc(&B, (void**)&ddem, (size_t)chunk * n * sizeof(uint64_t)));
+    TRY(route_source_open(&src, c, opts, algo, nsub, dm->verts));
+    st = src.st;
+    narcs = src.narcs;
+    /* beside the source's rows: the load itself, and a u64 demand row per source row */
+    TRY(route_source_chunks(&src, (size_t)narcs * 8, (size_t)n * 8, want));
+    TRY(dalloc(&B, (void**)&ddem, (size_t)src.chunk * n * sizeof(uint64_t)));
     TRY(dalloc(&B, (void**)&dload, (size_t)narcs * sizeof(uint64_t)));
     TRY(dalloc(&B, (void**)&dthrough, (size_t)n * sizeof(uint64_t)));
     TRY(dalloc(&B, (void**)&dtot, 3 * sizeof(uint64_t)));
@@ -2622,31 +2617,20 @@ static int link_load_one(const srt_canon* c, const srt_build_opts* opts, int alg
     TRYHIP(hipMemsetAsync(dthrough, 0, (size_t)n * sizeof(uint64_t), st));
     TRYHIP(hipMemsetAsync(dtot, 0, 3 * sizeof(uint64_t), st));
     if (dm->rowptr) { /* room for the COO entries of the largest chunk */
-        for (int r0 = 0; r0 < nsub; r0 += chunk) {
-            const int r1 = r0 + chunk < nsub ? r0 + chunk : nsub;
+        for (int r0 = 0; r0 < nsub; r0 += src.chunk) {
+            const int r1 = r0 + src.chunk < nsub ? r0 + src.chunk : nsub;
             const int64_t e = dm->rowptr[r1] - dm->rowptr[r0];
             max_ent = e > max_ent ? e : max_ent;
         }
-        TRY(dalloc(&B, (void**)&drowptr, ((size_t)chunk + 1) * sizeof(int64_t)));
+        TRY(dalloc(&B, (void**)&drowptr, ((size_t)src.chunk + 1) * sizeof(int64_t)));
         TRY(dalloc(&B, (void**)&dtgt, (size_t)max_ent * sizeof(int32_t)));
         TRY(dalloc(&B, (void**)&dval, (size_t)max_ent * sizeof(uint64_t)));
-        rel_rowptr.resize((size_t)chunk + 1);
+        rel_rowptr.resize((size_t)src.chunk + 1);
     }
-    for (int r0 = 0; r0 < nsub; r0 += chunk) {
-        const int cnt = r0 + chunk < nsub ? chunk : nsub - r0;
-        const int32_t* cs = verts ? dverts + r0 : NULL;
-        if (dense) {
-            TRY(srt_routes_rows_timed(n, cnt, cs, r0, 1, dlat, (size_t)ld, irp, icol, iw, dpred, NULL,
-                                      dhops, (size_t)n, st, &local));
-        } else {
-            memset(&bs, 0, sizeof(bs));
-            TRY(verts ? sparse_rows(sg, 0, cnt, cs, dlat, drel, NULL, st, &bs)
-                      : sparse_rows(sg, r0, r0 + cnt, NULL, dlat, drel, NULL, st, &bs));
-            local.ms_tables += bs.ms_total;
-            TRY(srt_routes_rows_timed(n, cnt, cs, r0, 0, dlat, (size_t)n, sg->irp, sg->icol, sg->iw,
-                                      dpred, NULL, dhops, (size_t)n, st, &local));
-        }
-        if (dm->rowptr) {
+    for (int r0 = 0; r0 < nsub; r0 += src.chunk) {
+        TRY(route_source_step(&src, r0));
+        const int cnt = src.cnt;
+        if (dm->rowptr) { /* the chunk's entries, their row offsets re-based to its first row */
             const int64_t e0 = dm->rowptr[r0], ne = dm->rowptr[r0 + cnt] - e0;
             for (int i = 0; i <= cnt; i++) rel_rowptr[i] = dm->rowptr[r0 + i] - e0;
             TRYHIP(hipMemcpyAsync(drowptr, rel_rowptr.data(), ((size_t)cnt + 1) * sizeof(int64_t),
@@ -2660,16 +2644,16 @@ static int link_load_one(const srt_canon* c, const srt_build_opts* opts, int alg
             TRYHIP(hipStreamSynchronize(st)); /* rel_rowptr is reused by the next chunk */
         }
         TRY(srt_link_load_demand_rows(n, cnt, drowptr, dtgt, dval, ddem, (size_t)n, st));
-        TRY(srt_link_load_rows(n, cnt, cs, r0, dpred, dhops, (size_t)n, ddem, (size_t)n, lirp, licol,
-                               dload, dthrough, dense && c->directed ? 0 : 1, dtot, st, &mh, &forms,
-                               &ll->ms_load));
+        TRY(srt_link_load_rows(n, cnt, src.srcs, r0, src.dout[0], src.dout[2], (size_t)n, ddem,
+                               (size_t)n, src.irp, src.icol, dload, dthrough, src.sorted, dtot, st,
+                               &mh, &forms, &ll->ms_load));
     }
     hirp.resize((size_t)n + 1);
     hicol.resize((size_t)(narcs > 0 ? narcs : 1));
     hload.resize((size_t)(narcs > 0 ? narcs : 1));
-    TRYHIP(hipMemcpyAsync(hirp.data(), lirp, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    TRYHIP(hipMemcpyAsync(hirp.data(), src.irp, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     if (narcs > 0) {
-        TRYHIP(hipMemcpyAsync(hicol.data(), licol, (size_t)narcs * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        TRYHIP(hipMemcpyAsync(hicol.data(), src.icol, (size_t)narcs * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         TRYHIP(hipMemcpyAsync(hload.data(), dload, (size_t)narcs * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     }
     TRYHIP(hipMemcpyAsync(ll->through, dthrough, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
@@ -2679,17 +2663,12 @@ static int link_load_one(const srt_canon* c, const srt_build_opts* opts, int alg
     ll->routed = htot[0];
     ll->unrouted = htot[1];
     ll->self_demand = htot[2];
-    ll->ms_tables = local.ms_tables;
-    ll->ms_routes = local.ms_routes;
+    ll->ms_tables = src.stats.ms_tables;
+    ll->ms_routes = src.stats.ms_routes;
     ll->max_hops = mh;
     ll->forms = forms;
 out:
-    if (st) {
-        srt_routes_ess_free(irp, icol, iw, st);
-        (void)hipStreamSynchronize(st);
-        (void)hipStreamDestroy(st);
-    }
-    srt_sparse_graph_free(sg);
+    route_source_close(&src);
     dfree(&B);
     return rc;
 }
@@ -2748,6 +2727,7 @@ extern "C" int srt_build_link_load(const srt_edges* g, const srt_build_opts* opt
         srt_set_error("srt_build_link_load: null argument");
         return SRT_E_ARG;
     }
+    last_row_chunks.store(0, std::memory_order_relaxed);
     const int n = g->n;
     ll_demand dm = {0, NULL, NULL, NULL, NULL};
     std::vector<int32_t> dverts;
@@ -2809,37 +2789,16 @@ extern "C" int srt_build_link_load(const srt_edges* g, const srt_build_opts* opt
         srt_set_error("srt_build_link_load: no HIP device");
         rc = SRT_E_DEVICE;
     } else {
-        /* the table build's own route to an algorithm, as srt_build_routes */
-        const int forced = opts ? opts->algo : SRT_ALGO_AUTO;
-        int edge_form = 0;
-        if (forced != SRT_ALGO_SPARSE_SSSP && g->n <= SRT_DENSE_MAX_N && g->m > 0) {
-            const double nn = g->n, ub = (double)g->m * (g->directed ? 1 : 2);
-            edge_form = g->n <= 2048 || ub * 16.0 >= nn * nn || forced == SRT_ALGO_DENSE_FW;
-        }
-        for (int attempt = 0; attempt < 2; attempt++) {
-            srt_canon c;
-            if (edge_form && attempt == 0 && canon_from_edges(g, &c) == 0) {
-                c.verify_dense = forced != SRT_ALGO_DENSE_FW;
-            } else {
-                if (attempt == 0) edge_form = 0;
-                rc = srt_canon_build(g, &c);
-                if (rc) break;
-            }
-            const int algo = c.wide && forced != SRT_ALGO_DENSE_FW ? SRT_ALGO_SPARSE_SSSP
-                                                                    : choose_algo(&c, opts);
-            if (c.wide) {
+        rc = with_canon(g, opts, 1, [&](const srt_canon* c, int algo, double) {
+            if (c->wide) {
                 srt_set_error("srt_build_link_load: shortest-path latencies may pass the u32 range "
                               "(bound %llu quanta of %llu ns); the route pass reads u32 rows only",
-                              (unsigned long long)c.dist_bound, (unsigned long long)c.quantum_ns);
-                srt_canon_free(&c);
-                rc = SRT_E_RANGE;
-                break;
+                              (unsigned long long)c->dist_bound, (unsigned long long)c->quantum_ns);
+                return (int)SRT_E_RANGE;
             }
             ll->ms_load = 0;
-            rc = link_load_one(&c, opts, algo, &dm, ll);
-            srt_canon_free(&c);
-            if (rc != SRT_FALLBACK_CANON) break;
-        }
+            return link_load_one(c, opts, algo, &dm, ll);
+        });
     }
     if (rc) {
         srt_link_load_free(ll);

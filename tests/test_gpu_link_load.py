@@ -5,27 +5,52 @@ Every case compares (tail, head, load) and through with the reference bit for bi
 demand totals, max_hops, and the identity sum(load) == sum(c * hops). Integers only: no tolerance
 anywhere.
 """
+import contextlib
 import functools
 
 import numpy as np
 import pytest
 
+from conftest import form_env
 import load_reference as lr
 import route_graphs
 from shadow_amd import graphs
 from shadow_amd._lib import ALGO_AUTO, ALGO_DENSE_FW, ALGO_SPARSE_SSSP, lib
-from shadow_amd.topology import build_link_load
+from shadow_amd.topology import build_link_load, build_routes
 
 pytestmark = pytest.mark.gpu
 MS = 1_000_000
 
 
-def check(g, algo=ALGO_AUTO, sources=None, demand=None):
-    """Build on the device, compare with the reference; returns (arcs dict, through, stats)."""
-    got = build_link_load(g.n, g.directed, g.src, g.dst, g.lat_ns, g.loss,
-                          sources=None if isinstance(demand, tuple) else sources, demand=demand,
-                          algo=algo)
+def canon_arcs(g):
+    """The arcs of the canonical graph: the distinct pairs off the diagonal, both ways when the
+    graph is undirected."""
+    off = g.src != g.dst
+    a, b = g.src[off].astype(np.int64), g.dst[off].astype(np.int64)
+    if g.directed:
+        return len(np.unique(a * g.n + b))
+    return 2 * len(np.unique(np.minimum(a, b) * g.n + np.maximum(a, b)))
+
+
+def check(g, algo=ALGO_AUTO, sources=None, demand=None, load_arcs=None):
+    """Build on the device, compare with the reference; returns (arcs dict, through, stats).
+    load_arcs: the arcs of the CSR the load is indexed by. When given, the build runs under
+    SRT_FORM memcap=1: 1 MiB free is below the reserve, so the budget is half of what the u64 load
+    leaves of it, and the rows must come in three chunks or more with a short last one."""
+    with form_env(memcap=1) if load_arcs is not None else contextlib.nullcontext():
+        got = build_link_load(g.n, g.directed, g.src, g.dst, g.lat_ns, g.loss,
+                              sources=None if isinstance(demand, tuple) else sources,
+                              demand=demand, algo=algo)
+        chunks = lib().srt_last_row_chunks()
     tail, head, load, through, st = got
+    if load_arcs is not None:
+        # per row and vertex: pred, hops and the u64 demand; a sparse build's distance and
+        # reliability rows too
+        rows = g.n if sources is None else len(sources)
+        row_bytes = (16 if algo == ALGO_DENSE_FW else 28) * g.n
+        chunk = ((1 << 20) - 8 * load_arcs) // 2 // row_bytes
+        print(f"{g.name} algo={algo}: {rows} rows, {chunk} a chunk, {chunks} chunks")
+        assert chunks >= 3 and chunks == -(-rows // chunk) and rows % chunk != 0, (chunks, chunk)
     ref = lr.reference(g, sources, demand)
     wt, wh, wl, wthr = ref.arrays()
     what = f"{g.name} algo={algo}"
@@ -81,10 +106,7 @@ def test_sparse_directed(gpu, ring):
     assert len(arcs) == (2_021 if ring else 1_881)
 
 
-def test_sparse_source_list_wide_flows(gpu):
-    """Case 4. 37 scattered sources and COO demands of 2^32 .. 2^45 each (duplicates and self
-    demand among them): every row's total is at least 2^32, so every row keeps u64 flow words in
-    LDS (form 2)."""
+def _wide_flows():
     g = graphs.random_geometric(2000, seed=3)
     srcs = np.unique(np.random.default_rng(5).integers(0, g.n, 60))[:37]
     assert len(srcs) == 37
@@ -94,7 +116,42 @@ def test_sparse_source_list_wide_flows(gpu):
     dtgt[::40] = srcs                      # self demand
     dtgt[1::40] = dtgt[2::40]              # a duplicate pair per source
     dval = rng.integers(1 << 32, 1 << 45, len(dsrc), dtype=np.uint64)
-    _, through, st = check(g, ALGO_SPARSE_SSSP, sources=srcs, demand=(dsrc, dtgt, dval))
+    return g, srcs, (dsrc, dtgt, dval)
+
+
+def test_sparse_source_list_wide_flows(gpu):
+    """Case 4. 37 scattered sources and COO demands of 2^32 .. 2^45 each (duplicates and self
+    demand among them): every row's total is at least 2^32, so every row keeps u64 flow words in
+    LDS (form 2)."""
+    g, srcs, dem = _wide_flows()
+    _, through, st = check(g, ALGO_SPARSE_SSSP, sources=srcs, demand=dem)
+    assert st.forms == 2, st.forms
+    assert st.self_demand >= 37 << 32 and int(through.max()) >= 1 << 32
+
+
+def test_several_row_chunks_dense_free_order(gpu):
+    """Case 2 with room for a few rows at a time: the load of every chunk adds into the same
+    unsorted in-lists (the essential arcs, which the route export counts)."""
+    g = route_graphs.complete_directed_holes()
+    ess = build_routes(g.n, True, g.src, g.dst, g.lat_ns, g.loss, algo=ALGO_DENSE_FW)[3].ess_arcs
+    _, _, st = check(g, ALGO_DENSE_FW, demand=lr.issue_demand(g.n), load_arcs=ess)
+    assert st.unrouted > 0 and st.forms == 1
+
+
+@pytest.mark.parametrize("ring", [True, False])
+def test_several_row_chunks_sparse(gpu, ring):
+    """Case 3 with room for a few rows at a time: every chunk's COO demand is re-based to its
+    first row."""
+    g = route_graphs.directed_random(ring)
+    _, _, st = check(g, ALGO_SPARSE_SSSP, demand=lr.issue_demand(g.n), load_arcs=canon_arcs(g))
+    assert st.self_demand == 84_584 and st.unrouted == (0 if ring else 376_938)
+
+
+def test_several_row_chunks_source_list(gpu):
+    """Case 4 with room for a few rows at a time: a source list and COO entries (duplicates and
+    self demand among them) cut at chunk boundaries; the flow words stay u64."""
+    g, srcs, dem = _wide_flows()
+    _, through, st = check(g, ALGO_SPARSE_SSSP, sources=srcs, demand=dem, load_arcs=canon_arcs(g))
     assert st.forms == 2, st.forms
     assert st.self_demand >= 37 << 32 and int(through.max()) >= 1 << 32
 

@@ -5,6 +5,7 @@ pred is compared with oracle.sssp_rows(want_pred=True)["pred"] exactly, over eve
 first and hops with route_reference.walk of the oracle's predecessors; stats.max_hops with the
 reference's maximum. Integers only: no tolerance anywhere.
 """
+import contextlib
 import ctypes
 import functools
 
@@ -12,6 +13,7 @@ import numpy as np
 import pytest
 
 import oracle
+from conftest import form_env
 import route_graphs
 import route_reference as rr
 from shadow_amd import graphs
@@ -51,10 +53,19 @@ def assert_routes(got, want, what, stats=None):
         assert stats.max_hops == int(want[2].max()), (what, stats.max_hops, int(want[2].max()))
 
 
-def run(g, algo=ALGO_AUTO, sources=None, **kw):
-    pred, first, hops, st = build_routes(g.n, g.directed, g.src, g.dst, g.lat_ns, g.loss,
-                                         sources=sources, algo=algo, **kw)
+def run(g, algo=ALGO_AUTO, sources=None, row_bytes=None, **kw):
+    """row_bytes: what one source row takes of the chunk budget per vertex. When given, the build
+    runs under SRT_FORM memcap=1: 1 MiB free is below the reserve, so the budget is half of it, and
+    the rows must come in three chunks or more with a short last one."""
+    with form_env(memcap=1) if row_bytes else contextlib.nullcontext():
+        pred, first, hops, st = build_routes(g.n, g.directed, g.src, g.dst, g.lat_ns, g.loss,
+                                             sources=sources, algo=algo, **kw)
+        chunks = lib().srt_last_row_chunks()
     assert_routes((pred, first, hops), expect(g, sources), f"{g.name} algo={algo}", st)
+    if row_bytes:
+        rows, chunk = len(pred), (1 << 19) // (row_bytes * g.n)
+        print(f"{g.name} algo={algo}: {rows} rows, {chunk} a chunk, {chunks} chunks")
+        assert chunks >= 3 and chunks == -(-rows // chunk) and rows % chunk != 0, (chunks, chunk)
     return pred, first, hops, st
 
 
@@ -120,6 +131,21 @@ def test_sparse_scattered_sources(gpu):
     srcs = np.unique(np.random.default_rng(5).integers(0, g.n, 60))[:37]
     assert len(srcs) == 37
     run(g, ALGO_SPARSE_SSSP, sources=srcs)
+
+
+@pytest.mark.parametrize("case", ["sparse", "dense", "source_list"])
+def test_several_row_chunks(gpu, case):
+    """Cases 4, 2 and 5 with room for a few rows at a time: the chunks' row offsets, the short last
+    chunk and the per-chunk downloads. A sparse row takes its distance and reliability (12 B a
+    vertex) beside the three outputs; a dense build's tables are already on the device."""
+    if case == "sparse":
+        run(route_graphs.directed_random(True), ALGO_SPARSE_SSSP, row_bytes=24)
+    elif case == "dense":
+        run(graphs.complete_graph(300, seed=11, lat_max=3), ALGO_DENSE_FW, row_bytes=12)
+    else:
+        g = graphs.random_geometric(2000, seed=3)
+        srcs = np.unique(np.random.default_rng(5).integers(0, g.n, 60))[:37]
+        run(g, ALGO_SPARSE_SSSP, sources=srcs, row_bytes=24)
 
 
 @functools.lru_cache(maxsize=None)

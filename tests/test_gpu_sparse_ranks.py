@@ -5,12 +5,15 @@ copies), so the schedule, the shard boundaries and the gather run as they would 
 
 Against oracle.sssp_list (the restatement of topology.c:1578-1814's per-source Dijkstra):
 latency bit-exact in integer ns, reliability within 1e-12 relative (north_star)."""
+import ctypes
+
 import numpy as np
 import pytest
 
+from conftest import form_env
 import oracle
 from shadow_amd import graphs
-from shadow_amd._lib import ALGO_AUTO, ALGO_SPARSE_SSSP
+from shadow_amd._lib import ALGO_AUTO, ALGO_SPARSE_SSSP, BuildOpts, BuildStats, Edges, check, lib
 from shadow_amd.topology import build_tables, build_tables_subset
 
 pytestmark = pytest.mark.gpu
@@ -69,3 +72,57 @@ def test_c3_full_table_four_virtual_ranks(gpu, monkeypatch):
         worst = max(worst, _rel_err(np.where(off, rel[s0:s1], 1.0),
                                     np.where(off, exp["rel"], 1.0)))
     assert worst <= REL_TOL, worst
+
+
+def _subset_counting_ties(g, verts, ngpus=1, want_ms=False):
+    """srt_build_tables_subset with srt_build_stats.count_ties set (build_tables_subset leaves it
+    0) -> (lat quanta [k, k], rel, lat_ms or None, min quanta, stats, row chunks)."""
+    e = Edges(g.n, int(g.directed), len(g.src), g.src.ctypes.data, g.dst.ctypes.data,
+              g.lat_ns.ctypes.data, g.loss.ctypes.data)
+    o = BuildOpts(0, ALGO_SPARSE_SSSP, 1, 0)
+    k = len(verts)
+    lat = np.empty((k, k), np.uint32)
+    rel = np.empty((k, k), np.float64)
+    ms = np.empty((k, k), np.float64) if want_ms else None
+    q, mn, st = ctypes.c_uint64(), ctypes.c_uint32(), BuildStats()
+    st.count_ties = 1
+    check(lib().srt_build_tables_subset(ctypes.byref(e), ctypes.byref(o), ngpus, k,
+                                        verts.ctypes.data, lat.ctypes.data, ctypes.byref(q),
+                                        rel.ctypes.data, None if ms is None else ms.ctypes.data,
+                                        ctypes.byref(mn), ctypes.byref(st)),
+          "srt_build_tables_subset")
+    return lat.astype(np.uint64) * np.uint64(q.value), rel, ms, mn.value, st, \
+        lib().srt_last_row_chunks()
+
+
+def test_attached_rows_in_several_chunks(gpu, monkeypatch):
+    """101 attached vertices of a 2,000-vertex RGG with room for a few source rows at a time
+    (SRT_FORM memcap=1: 1 MiB free is below the reserve, so the budget is half of it, shared by
+    the virtual ranks): on one GPU, with the f64 ms rows beside them, and on 2 virtual ranks. The
+    chunks' offsets into the sub-table, the short last chunk and the statistics added over the
+    chunks: the same tables, minimum and tied pairs as the build that takes every row at once,
+    and the oracle's rows."""
+    g = graphs.random_geometric(2000, seed=3)
+    verts = np.unique(np.random.default_rng(17).integers(0, g.n, 150))[:101].astype(np.int32)
+    assert len(verts) == 101
+    lat0, rel0, ms0, mn0, st0, chunks0 = _subset_counting_ties(g, verts, want_ms=True)
+    assert chunks0 == 1 and st0.tied_pairs > 0
+
+    def chunked(rows, sharers=1, row_bytes=12, **kw):
+        with form_env(memcap=1):
+            lat, rel, ms, mn, st, chunks = _subset_counting_ties(g, verts, **kw)
+        chunk = (1 << 19) // sharers // (row_bytes * g.n)
+        print(f"{kw}: {rows} rows, {chunk} a chunk, {chunks} chunks, tied {st.tied_pairs}")
+        assert chunks >= 3 and chunks == -(-rows // chunk) and rows % chunk != 0, (chunks, chunk)
+        assert np.array_equal(lat, lat0) and np.array_equal(rel, rel0) and mn == mn0
+        assert st.algo == ALGO_SPARSE_SSSP and st.tied_pairs == st0.tied_pairs
+        return ms
+
+    chunked(101)
+    assert np.array_equal(chunked(101, row_bytes=20, want_ms=True), ms0)
+    monkeypatch.setenv("SRT_VIRTUAL_RANKS", "2")
+    chunked(51, sharers=2, ngpus=2)  # rank 0 holds 51 of the 101 slots
+    rows = oracle.sssp_list(_el(g), verts, nthreads=16)
+    off = ~np.eye(len(verts), dtype=bool)
+    assert np.array_equal(lat0[off], rows["lat_int"][:, verts][off])
+    assert _rel_err(rel0[off], rows["rel"][:, verts][off]) <= REL_TOL
