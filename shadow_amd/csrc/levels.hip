@@ -47,6 +47,7 @@
 #define LVL_PB 12 /* lvl_pred_kernel: gathers per pipelined batch */
 #define LVL_NEAR_NW 2048 /* lvl_near_kernel: a target's plane row in LDS, four per workgroup */
 #define LVL_NEAR_MIN_NW 512 /* ... and only for shares of at least 16,384 sources */
+#define LVL_ROWS_MIN_ROUNDS 16u /* lvl_pred_rows_kernel: multi-sub-chunk units keep this many rounds */
 
 /* ---- in-arc extraction ------------------------------------------------------------------- */
 /* COUNT: per (target, weight) histogram of arcs with 1 <= w <= LVL_WMAX; FILL: the arcs (k | w << 16)
@@ -1074,6 +1075,14 @@ __global__ void lvl_aoff_kernel(int total, int nw, const uint32_t* __restrict__ 
     if (i < total) aoff[i] = (arcs[i] & 0xFFFFu) * (uint32_t)nw * 4u;
 }
 
+/* lvl_pred_rows_kernel's output stage: each arc's source vertex | index into rtab << 16, the low
+ * 27 bits of a packed word, so a pair costs one gather where arcs[] and rix[] were two */
+__global__ void lvl_apk_kernel(int total, const uint32_t* __restrict__ arcs,
+                               const uint16_t* __restrict__ rix, uint32_t* __restrict__ apk) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < total) apk[i] = (arcs[i] & 0xFFFFu) | (uint32_t)rix[i] << 16;
+}
+
 /* ---- the levels ---------------------------------------------------------------------------- */
 /* R = {j} for the local sources j (distance 0), everything else empty */
 __global__ void lvl_init_kernel(int n, int src0, int nsrc, int nw, uint32_t* __restrict__ R) {
@@ -1847,7 +1856,13 @@ __global__ __launch_bounds__(256, 7) void lvl_pred_kernel(int n, int nw, int nch
  *    the lane that owns the arc's source (one ds_bpermute) and writes that lane's sidx entry and
  *    claimed bit through LDS;
  *  - lvl_pred_near_kernel's buckets stay keyed by (target, 2,048-source chunk): a group reads
- *    the bucket of its enclosing chunk and keeps the entries of its sub-chunk's sources.
+ *    the bucket of its enclosing chunk and keeps the entries of its sub-chunk's sources;
+ *  - a workgroup walks up to four sub-chunks of one chunk back to back for its 16 targets (the
+ *    unit loop below; the rule for the run length is srt_levels_pred's);
+ *  - the output stage reads one word per pair, apk[k] = source | rix << 16 (lvl_apk_kernel, once
+ *    per build), where lvl_pred_unit gathers arcs[k] and rix[k]. C4, the kernel per launch as
+ *    bench.py times it: 5.60 ms, 5.45 with the arc word, 5.37 with whole-chunk units on top
+ *    (which alone measured no gain: DESIGN 5.7).
  * LDS per lane, LVL_RW_LANE = 22 words: 16 of sidx (32 u16) and the claimed word; words 17.. are
  * idle during the walk and hold the target's group bounds off[t][0 .. 32] (31 levels at most:
  * weight w's bound is in lane w % WPT, word 17 + w / WPT); after the walk, behind a wave-level
@@ -1861,11 +1876,11 @@ __global__ __launch_bounds__(256, 7) void lvl_pred_kernel(int n, int nw, int nch
 #define LVL_RW_LANE 22
 template <int TPW, int NWV, int PB>
 __global__ __launch_bounds__(NWV * 64, NWV == 4 ? 7 : 6) void lvl_pred_rows_kernel(
-    int n, int nw, int nchunk, int src0, int nsrc, int nlev, unsigned ntg, unsigned nunit,
+    int n, int nw, int nchunk, int src0, int nsrc, int nlev, unsigned ntg, unsigned nunit, int S,
     const int32_t* __restrict__ off, const uint32_t* __restrict__ arcs, const uint32_t* __restrict__ aoff,
-    const uint16_t* __restrict__ rix, const uint32_t* __restrict__ lev, uint32_t* __restrict__ pk, size_t ld,
+    const uint32_t* __restrict__ apk, const uint32_t* __restrict__ lev, uint32_t* __restrict__ pk, size_t ld,
     const uint32_t* __restrict__ bkt, const uint32_t* __restrict__ bcnt, int cap) {
-    constexpr int WPT = 64 / TPW;                 /* words (lanes) per target */
+    constexpr int WPT = 64 / TPW;                /* words (lanes) per target */
     constexpr int NT = TPW * NWV;                  /* targets per workgroup */
     constexpr int SUB = WPT * 32;                  /* sources per sub-chunk */
     constexpr int TGT = WPT * LVL_RW_LANE + 4;     /* a target's words: its lanes' and the padding */
@@ -1888,176 +1903,186 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? 7 : 6) void lvl_pred_rows_kern
     auto gany = [&](bool p) -> bool {
         return ((__ballot(p) >> (lane & (64 - WPT))) & ((1ull << WPT) - 1ull)) != 0ull;
     };
-    /* chunk-major, consecutive workgroups (one per XCD in turn) on consecutive target groups:
-     * the whole GPU gathers from one sub-chunk's slices at a time */
+    /* A unit is (target group, run of S consecutive sub-chunks of one 2,048-source chunk; S 1, 2
+     * or 4, so a run never leaves its chunk): the workgroup keeps its NT targets and walks the
+     * run's sub-chunks back to back, so the bounds, the arc offsets, the bucket and the arcs[] /
+     * rix[] lines of its targets, the same for every sub-chunk of the chunk, are read again by
+     * the workgroup that had them moments ago. Run-major, consecutive workgroups (one per XCD
+     * in turn) on consecutive target groups: the whole GPU gathers from one run's slices at a
+     * time. Everything a sub-chunk leaves in the tile or in registers is rebuilt for the next. */
+    const int nsub = (nw + WPT - 1) / WPT;
     for (unsigned u = blockIdx.x; u < nunit; u += gridDim.x) {
-        const int c16 = (int)(u / ntg), tg = (int)(u % ntg);
-        const int t = tg * NT + gl, word = c16 * WPT + l;
-        const bool tv = t < n, act = tv && word < nw;
-        const int cs0 = c16 * SUB; /* the sub-chunk's first local source */
+        const int run = (int)(u / ntg), tg = (int)(u % ntg);
+        const int t = tg * NT + gl;
+        const bool tv = t < n;
+        for (int c16 = run * S, ce = min(c16 + S, nsub); c16 < ce; ++c16) {
+            const int word = c16 * WPT + l;
+            const bool act = tv && word < nw;
+            const int cs0 = c16 * SUB; /* the sub-chunk's first local source */
 #pragma unroll
-        for (int q = 0; q < 16; q += 2) /* (a lane's words are 8-B aligned: 22 words apart) */
-            *reinterpret_cast<uint2*>(mine + q) = make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
-        mine[16] = 0u;
-        {
-            const int32_t* ot = off + (size_t)(tv ? t : 0) * LVL_STRIDE;
+            for (int q = 0; q < 16; q += 2) /* (a lane's words are 8-B aligned: 22 words apart) */
+                *reinterpret_cast<uint2*>(mine + q) = make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
+            mine[16] = 0u;
+            {
+                const int32_t* ot = off + (size_t)(tv ? t : 0) * LVL_STRIDE;
 #pragma unroll
-            for (int k = 0; k < NB; ++k) mine[17 + k] = tv ? (uint32_t)ot[k * WPT + l] : 0u;
-            if (l == 0) tgt[WPT * LVL_RW_LANE] = tv ? (uint32_t)ot[0] : 0u;
-        }
-        wave_sync();
-        auto otl = [&](int w) -> int { return (int)tgt[(w & (WPT - 1)) * LVL_RW_LANE + 17 + w / WPT]; };
-        const int a_t = otl(0);
-        const uint32_t lane4 = (uint32_t)(act ? word : 0) * 4u;
-        /* the bucket of (t, enclosing chunk): the entries of this sub-chunk's sources into
-         * their owners' sidx slots and claimed words. An overflowed bucket is ignored. */
-        bool pn = false;
-        if (bkt) {
-            const size_t un = (size_t)(tv ? t : 0) * nchunk + c16 / (2048 / SUB);
-            const int k = tv ? (int)bcnt[un] : cap + 1;
-            pn = k <= cap;
-            const uint32_t* ub = bkt + un * cap;
-            for (int i = l; pn && i < k; i += WPT) {
-                const uint32_t e = ub[i], sl = e & 2047u;
-                if ((int)(sl / SUB) != (c16 & (2048 / SUB - 1))) continue;
-                uint32_t* o = tgt + ((sl >> 5) & (uint32_t)(WPT - 1)) * LVL_RW_LANE;
-                reinterpret_cast<uint16_t*>(o)[sl & 31u] = (uint16_t)(e >> 11);
-                atomicOr(&o[16], 1u << (sl & 31u));
+                for (int k = 0; k < NB; ++k) mine[17 + k] = tv ? (uint32_t)ot[k * WPT + l] : 0u;
+                if (l == 0) tgt[WPT * LVL_RW_LANE] = tv ? (uint32_t)ot[0] : 0u;
             }
             wave_sync();
-        }
-        uint32_t lvb[5] = {0u, 0u, 0u, 0u, 0u};
-        for (int d = 1; d <= nlev; ++d) {
-            uint32_t pend = act ? lev[(size_t)(d - 1) * plane + (size_t)t * nw + word] : 0u;
+            auto otl = [&](int w) -> int { return (int)tgt[(w & (WPT - 1)) * LVL_RW_LANE + 17 + w / WPT]; };
+            const int a_t = otl(0);
+            const uint32_t lane4 = (uint32_t)(act ? word : 0) * 4u;
+            /* the bucket of (t, enclosing chunk): the entries of this sub-chunk's sources into
+             * their owners' sidx slots and claimed words. An overflowed bucket is ignored. */
+            bool pn = false;
+            if (bkt) {
+                const size_t un = (size_t)(tv ? t : 0) * nchunk + c16 / (2048 / SUB);
+                const int k = tv ? (int)bcnt[un] : cap + 1;
+                pn = k <= cap;
+                const uint32_t* ub = bkt + un * cap;
+                for (int i = l; pn && i < k; i += WPT) {
+                    const uint32_t e = ub[i], sl = e & 2047u;
+                    if ((int)(sl / SUB) != (c16 & (2048 / SUB - 1))) continue;
+                    uint32_t* o = tgt + ((sl >> 5) & (uint32_t)(WPT - 1)) * LVL_RW_LANE;
+                    reinterpret_cast<uint16_t*>(o)[sl & 31u] = (uint16_t)(e >> 11);
+                    atomicOr(&o[16], 1u << (sl & 31u));
+                }
+                wave_sync();
+            }
+            uint32_t lvb[5] = {0u, 0u, 0u, 0u, 0u};
+            for (int d = 1; d <= nlev; ++d) {
+                uint32_t pend = act ? lev[(size_t)(d - 1) * plane + (size_t)t * nw + word] : 0u;
 #pragma unroll
-            for (int k = 0; k < 5; ++k)
-                if ((d >> k) & 1) lvb[k] |= pend;
-            pend &= ~mine[16];
-            if (!__any(pend != 0u)) continue;
-            for (int w = d; w >= 1; --w) {
-                const bool gp = gany(pend != 0u);
-                const int g0 = otl(w);
-                int g1 = otl(w + 1);
-                if (!gp || (pn && w == d - 1)) g1 = g0; /* nothing pending, or the pre-pass took this group */
-                if (!__any(g0 < g1)) continue;
-                if (w == d) {
-                    /* the direct arc (u, t): tight for the source u itself; distinct arcs have
-                     * distinct sources, so the order does not matter */
-                    for (int i0 = g0; __any(i0 < g1); i0 += WPT) {
-                        const int i = i0 + l;
-                        const int us = i < g1 ? (int)(arcs[i] & 0xFFFFu) - src0 : -1;
-                        const bool in = us >= 0 && us < nsrc && (unsigned)(us - cs0) < (unsigned)SUB;
-                        const int ow = in ? (us >> 5) & (WPT - 1) : 0;
-                        const uint32_t op = (uint32_t)__shfl((int)pend, ow, WPT);
-                        if (in && ((op >> (us & 31)) & 1u)) {
-                            uint32_t* o = tgt + ow * LVL_RW_LANE;
-                            reinterpret_cast<uint16_t*>(o)[us & 31] = (uint16_t)(i - a_t);
-                            atomicOr(&o[16], 1u << (us & 31));
+                for (int k = 0; k < 5; ++k)
+                    if ((d >> k) & 1) lvb[k] |= pend;
+                pend &= ~mine[16];
+                if (!__any(pend != 0u)) continue;
+                for (int w = d; w >= 1; --w) {
+                    const bool gp = gany(pend != 0u);
+                    const int g0 = otl(w);
+                    int g1 = otl(w + 1);
+                    if (!gp || (pn && w == d - 1)) g1 = g0; /* nothing pending, or the pre-pass took this group */
+                    if (!__any(g0 < g1)) continue;
+                    if (w == d) {
+                        /* the direct arc (u, t): tight for the source u itself; distinct arcs have
+                         * distinct sources, so the order does not matter */
+                        for (int i0 = g0; __any(i0 < g1); i0 += WPT) {
+                            const int i = i0 + l;
+                            const int us = i < g1 ? (int)(arcs[i] & 0xFFFFu) - src0 : -1;
+                            const bool in = us >= 0 && us < nsrc && (unsigned)(us - cs0) < (unsigned)SUB;
+                            const int ow = in ? (us >> 5) & (WPT - 1) : 0;
+                            const uint32_t op = (uint32_t)__shfl((int)pend, ow, WPT);
+                            if (in && ((op >> (us & 31)) & 1u)) {
+                                uint32_t* o = tgt + ow * LVL_RW_LANE;
+                                reinterpret_cast<uint16_t*>(o)[us & 31] = (uint16_t)(i - a_t);
+                                atomicOr(&o[16], 1u << (us & 31));
+                            }
                         }
-                    }
-                    wave_sync();
-                    pend &= ~mine[16];
-                } else {
-                    /* PB gathers per batch, software-pipelined as lvl_pred_unit's; e is the
-                     * group's end of the walk, pulled in once none of its sources is pending */
-                    const char* base = reinterpret_cast<const char*>(lev + (size_t)(d - w - 1) * plane);
-                    int i = g0, e = g1;
-                    uint32_t v[PB], vn[PB];
-                    {
-                        const uint32_t aq = l < PB && i + l < e ? aoff[i + l] : 0u;
-#pragma unroll
-                        for (int q = 0; q < PB; ++q) {
-                            const uint32_t a = (uint32_t)__shfl((int)aq, q, WPT);
-                            v[q] = i + q < e ? *reinterpret_cast<const uint32_t*>(base + (a + lane4)) : 0u;
-                        }
-                    }
-                    while (__any(i < e)) {
-                        const int i2 = i + PB;
+                        wave_sync();
+                        pend &= ~mine[16];
+                    } else {
+                        /* PB gathers per batch, software-pipelined as lvl_pred_unit's; e is the
+                         * group's end of the walk, pulled in once none of its sources is pending */
+                        const char* base = reinterpret_cast<const char*>(lev + (size_t)(d - w - 1) * plane);
+                        int i = g0, e = g1;
+                        uint32_t v[PB], vn[PB];
                         {
-                            const uint32_t aq = l < PB && i2 + l < e ? aoff[i2 + l] : 0u;
+                            const uint32_t aq = l < PB && i + l < e ? aoff[i + l] : 0u;
 #pragma unroll
                             for (int q = 0; q < PB; ++q) {
                                 const uint32_t a = (uint32_t)__shfl((int)aq, q, WPT);
-                                vn[q] = i2 + q < e ? *reinterpret_cast<const uint32_t*>(base + (a + lane4)) : 0u;
+                                v[q] = i + q < e ? *reinterpret_cast<const uint32_t*>(base + (a + lane4)) : 0u;
                             }
                         }
+                        while (__any(i < e)) {
+                            const int i2 = i + PB;
+                            {
+                                const uint32_t aq = l < PB && i2 + l < e ? aoff[i2 + l] : 0u;
 #pragma unroll
-                        for (int q = 0; q < PB; ++q) { /* a source takes its first tight arc */
-                            uint32_t nb = v[q] & pend;
-                            pend &= ~nb;
-                            while (nb) {
-                                my[__builtin_ctz(nb)] = (uint16_t)(i + q - a_t);
-                                nb &= nb - 1u;
+                                for (int q = 0; q < PB; ++q) {
+                                    const uint32_t a = (uint32_t)__shfl((int)aq, q, WPT);
+                                    vn[q] = i2 + q < e ? *reinterpret_cast<const uint32_t*>(base + (a + lane4)) : 0u;
+                                }
                             }
-                        }
 #pragma unroll
-                        for (int q = 0; q < PB; ++q) v[q] = vn[q];
-                        i = i2;
-                        if (!gany(pend != 0u)) e = min(e, i);
+                            for (int q = 0; q < PB; ++q) { /* a source takes its first tight arc */
+                                uint32_t nb = v[q] & pend;
+                                pend &= ~nb;
+                                while (nb) {
+                                    my[__builtin_ctz(nb)] = (uint16_t)(i + q - a_t);
+                                    nb &= nb - 1u;
+                                }
+                            }
+#pragma unroll
+                            for (int q = 0; q < PB; ++q) v[q] = vn[q];
+                            i = i2;
+                            if (!gany(pend != 0u)) e = min(e, i);
+                        }
                     }
+                    if (!__any(pend != 0u)) break;
                 }
-                if (!__any(pend != 0u)) break;
             }
-        }
-        wave_sync(); /* the bounds' last read (another lane's words 17..) before the planes */
+            wave_sync(); /* the bounds' last read (another lane's words 17..) before the planes */
 #pragma unroll
-        for (int k = 0; k < 5; ++k) mine[16 + k] = lvb[k];
-        __syncthreads();
-        /* Output: thread (tq = thread % NQ, octet = thread / NQ) takes 8 consecutive sources --
-         * bits oct * 8.. of word wd, octet = 4 * wd + oct -- of targets 4 * tq .. + 3: one 16-B
-         * piece per source, the NQ tq lanes one source's run of NT * 4 B, so every store
-         * instruction writes 64 / NQ whole runs with consecutive lanes consecutive in memory.
-         * nsrc is a multiple of 128: whole groups of 8. */
-        {
-            constexpr int NQ = NT / 4;
-            const int tq = (int)threadIdx.x % NQ, kq = (int)threadIdx.x / NQ;
-            const int wd = kq >> 2, oct = kq & 3;
-            const int sl0 = cs0 + wd * 32 + oct * 8, t0 = tg * NT + 4 * tq;
-            if (sl0 < nsrc && t0 < n) {
-                uint32_t lq[4][5];
-                int at[4];
-                const uint32_t* ps = sw + (4 * tq) * TGT + wd * LVL_RW_LANE + oct * 4;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const uint32_t* p = sw + (4 * tq + j) * TGT;
-                    at[j] = (int)p[WPT * LVL_RW_LANE];
-                    p += wd * LVL_RW_LANE;
-                    const uint2 b0 = *reinterpret_cast<const uint2*>(p + 16);
-                    const uint2 b1 = *reinterpret_cast<const uint2*>(p + 18);
-                    lq[j][0] = b0.x >> (oct * 8), lq[j][1] = b0.y >> (oct * 8);
-                    lq[j][2] = b1.x >> (oct * 8), lq[j][3] = b1.y >> (oct * 8);
-                    lq[j][4] = p[20] >> (oct * 8);
-                }
-                /* the sidx entries come from the tile a source pair at a time: held in registers
-                 * for all eight sources they are 12 more VGPRs than seven waves per SIMD leave */
-#pragma unroll 1
-                for (int e = 0; e < 8; ++e) {
-                    const int sg = src0 + sl0 + e;
-                    uint32_t kv[4];
+            for (int k = 0; k < 5; ++k) mine[16 + k] = lvb[k];
+            __syncthreads();
+            /* Output: thread (tq = thread % NQ, octet = thread / NQ) takes 8 consecutive sources --
+             * bits oct * 8.. of word wd, octet = 4 * wd + oct -- of targets 4 * tq .. + 3: one 16-B
+             * piece per source, the NQ tq lanes one source's run of NT * 4 B, so every store
+             * instruction writes 64 / NQ whole runs with consecutive lanes consecutive in memory.
+             * nsrc is a multiple of 128: whole groups of 8. */
+            {
+                constexpr int NQ = NT / 4;
+                const int tq = (int)threadIdx.x % NQ, kq = (int)threadIdx.x / NQ;
+                const int wd = kq >> 2, oct = kq & 3;
+                const int sl0 = cs0 + wd * 32 + oct * 8, t0 = tg * NT + 4 * tq;
+                if (sl0 < nsrc && t0 < n) {
+                    uint32_t lq[4][5];
+                    int at[4];
+                    const uint32_t* ps = sw + (4 * tq) * TGT + wd * LVL_RW_LANE + oct * 4;
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        const uint32_t x = (ps[j * TGT + (e >> 1)] >> (16 * (e & 1))) & 0xFFFFu;
-                        const bool h = sg < n && sg != t0 + j && t0 + j < n && x != 0xFFFFu;
-                        const int k = at[j] + (h ? (int)x : 0);
-                        uint32_t lv = 0;
-#pragma unroll
-                        for (int kk = 0; kk < 5; ++kk) lv |= ((lq[j][kk] >> e) & 1u) << kk;
-                        kv[j] = h ? ((arcs[k] & 0xFFFFu) | (uint32_t)rix[k] << 16 | lv << 27) : 0xFFFFu;
+                        const uint32_t* p = sw + (4 * tq + j) * TGT;
+                        at[j] = (int)p[WPT * LVL_RW_LANE];
+                        p += wd * LVL_RW_LANE;
+                        const uint2 b0 = *reinterpret_cast<const uint2*>(p + 16);
+                        const uint2 b1 = *reinterpret_cast<const uint2*>(p + 18);
+                        lq[j][0] = b0.x >> (oct * 8), lq[j][1] = b0.y >> (oct * 8);
+                        lq[j][2] = b1.x >> (oct * 8), lq[j][3] = b1.y >> (oct * 8);
+                        lq[j][4] = p[20] >> (oct * 8);
                     }
-                    uint32_t* pp = pk + (size_t)(sl0 + e) * ld + t0;
-                    if (t0 + 3 < n) { /* non-temporal, as lvl_pred_unit's words */
-                        typedef unsigned u32x4n __attribute__((ext_vector_type(4)));
-                        __builtin_nontemporal_store((u32x4n){kv[0], kv[1], kv[2], kv[3]},
-                                                    reinterpret_cast<u32x4n*>(pp));
-                    } else {
+                    /* the sidx entries come from the tile a source pair at a time: held in registers
+                     * for all eight sources they are 12 more VGPRs than seven waves per SIMD leave */
+#pragma unroll 1
+                    for (int e = 0; e < 8; ++e) {
+                        const int sg = src0 + sl0 + e;
+                        uint32_t kv[4];
 #pragma unroll
-                        for (int j = 0; j < 4; ++j)
-                            if (t0 + j < n) pp[j] = kv[j];
+                        for (int j = 0; j < 4; ++j) {
+                            const uint32_t x = (ps[j * TGT + (e >> 1)] >> (16 * (e & 1))) & 0xFFFFu;
+                            const bool h = sg < n && sg != t0 + j && t0 + j < n && x != 0xFFFFu;
+                            const int k = at[j] + (h ? (int)x : 0);
+                            uint32_t lv = 0;
+#pragma unroll
+                            for (int kk = 0; kk < 5; ++kk) lv |= ((lq[j][kk] >> e) & 1u) << kk;
+                            kv[j] = h ? (apk[k] | lv << 27) : 0xFFFFu;
+                        }
+                        uint32_t* pp = pk + (size_t)(sl0 + e) * ld + t0;
+                        if (t0 + 3 < n) { /* non-temporal, as lvl_pred_unit's words */
+                            typedef unsigned u32x4n __attribute__((ext_vector_type(4)));
+                            __builtin_nontemporal_store((u32x4n){kv[0], kv[1], kv[2], kv[3]},
+                                                        reinterpret_cast<u32x4n*>(pp));
+                        } else {
+#pragma unroll
+                            for (int j = 0; j < 4; ++j)
+                                if (t0 + j < n) pp[j] = kv[j];
+                        }
                     }
                 }
             }
+            __syncthreads(); /* the next sub-chunk's walk rewrites the tile */
         }
-        __syncthreads(); /* the next unit's walk rewrites the tile */
     }
 }
 
@@ -2154,6 +2179,7 @@ typedef struct {
     uint32_t* aoff;
     double* ar;
     uint16_t* rix; /* packed form: each arc's index into rtab (NULL: more than LVL_RT_CAP values) */
+    uint32_t* apk; /* pkw 1: each arc's source | rix << 16 (lvl_apk_kernel) */
     double* rtab;
     int ntab;
     uint32_t* lev;
@@ -3137,12 +3163,19 @@ int srt_levels_build(const srt_comm* comm, int n, int ld, int row0, int nrows, i
     /* the packed post pass writes the u32 rows itself (rel_pk_kernel): the table of distinct arc
      * reliabilities, 5-bit levels and u16 vertices (n <= 32768) */
     /* 1: the packed words with the level, source-major from lvl_pred_rows_kernel (with the tie
-     * count: as 2), then rel_pk_kernel, which writes the u32 rows too; 2 (SRT_FORM pkw=2):
+     * count: as 2), then rel_pk_kernel, which writes the u32 rows too (SRT_FORM pkw=3, 4: the
+     * same with srt_levels_pred's units forced to one sub-chunk, to whole chunks); 2 (SRT_FORM pkw=2):
      * lvl_pred_kernel's target-major words and one transpose before rel_pk_kernel; 0 (past the
      * packed form, or SRT_FORM pkw=0): lvl_out8 rows + the predecessor rows + rel_tree_kernel */
     const int fpkw = srt_form_int("pkw", 1);
     const int pkw = rix && D <= 31 && n <= 32768 ? (fpkw == 2 ? 2 : fpkw != 0) : 0;
     uint8_t* l8 = NULL;
+    uint32_t* apk = NULL;
+    if (pkw == 1 && total_x > 0) { /* 4 B per held arc (34 MB on C4), freed with the state */
+        LVL_ALLOC(apk, (size_t)total_x * sizeof(uint32_t));
+        lvl_apk_kernel<<<srt_ceil_div(total_x, 256), 256, 0, st>>>(total_x, arcs, rix, apk);
+        SRT_HIPCHK(hipGetLastError());
+    }
     if (!pkw) {
         LVL_ALLOC(l8, (size_t)nrows * ld);
         if (D <= LVL_OUT_L) {
@@ -3172,6 +3205,7 @@ int srt_levels_build(const srt_comm* comm, int n, int ld, int row0, int nrows, i
     L->aoff = aoff;
     L->ar = ar;
     L->rix = rix;
+    L->apk = apk;
     L->rtab = rtab;
     L->ntab = ntab;
     L->lev = lev;
@@ -3218,8 +3252,9 @@ int srt_levels_pred(void* predT, int pred16, double* rT, size_t ldp, unsigned lo
         srt_set_error("levels: the packed form needs the reliability table");
         return SRT_E_ARG;
     }
-    if (pred16 == 3 && (ties || L->D > 31)) {
-        srt_set_error("levels: the source-major packed words take no tie count and at most 31 levels");
+    if (pred16 == 3 && (ties || L->D > 31 || (!L->apk && L->total > 0))) {
+        srt_set_error("levels: the source-major packed words take no tie count, at most 31 levels and "
+                      "the build's arc words (pkw 1)");
         return SRT_E_ARG;
     }
     /* The Delta_1 groups from the in-arc runs first (lvl_pred_near_kernel), where the runs pay:
@@ -3260,10 +3295,20 @@ int srt_levels_pred(void* predT, int pred16, double* rT, size_t ldp, unsigned lo
         constexpr int TPW = 4, NWV = 4; /* 16 targets x 512 sources per workgroup of 256 threads */
         const auto kern = lvl_pred_rows_kernel<TPW, NWV, 8>;
         const unsigned ntg = (unsigned)srt_ceil_div(L->n, TPW * NWV);
-        const unsigned nunit = ntg * (unsigned)srt_ceil_div(L->nw, 64 / TPW);
-        kern<<<lvl_grid((const void*)kern, nunit, 0, NWV * 64), NWV * 64, 0, st>>>(
-            L->n, L->nw, L->nchunk, L->row0, L->nrows, L->D, ntg, nunit, L->off, L->arcs, L->aoff, L->rix,
-            L->lev, (uint32_t*)predT, ldp, bkt, bcnt, cap);
+        const unsigned nsub = (unsigned)srt_ceil_div(L->nw, 64 / TPW);
+        /* The sub-chunks a unit walks back to back, of the four of a 2,048-source chunk: the
+         * longest run that still leaves LVL_ROWS_MIN_ROUNDS rounds of units to the grid (the
+         * units are S times coarser, and a narrow share would pay for them in its last round:
+         * C4 on one GPU takes 4 and on N = 2 takes 2, at 18 rounds each; N >= 4 keeps 1).
+         * SRT_FORM pkw=3 / 4 (tests, A/B): one sub-chunk / whole chunks at any share. */
+        const unsigned full = lvl_grid((const void*)kern, ~0u, 0, NWV * 64);
+        const int fpkw = srt_form_int("pkw", 1);
+        unsigned S = fpkw == 3 ? 1u : 4u;
+        while (fpkw != 4 && S > 1 && ntg * ((nsub + S - 1) / S) < LVL_ROWS_MIN_ROUNDS * full) S >>= 1;
+        const unsigned nunit = ntg * ((nsub + S - 1) / S);
+        kern<<<min(full, nunit), NWV * 64, 0, st>>>(
+            L->n, L->nw, L->nchunk, L->row0, L->nrows, L->D, ntg, nunit, (int)S, L->off, L->arcs, L->aoff,
+            L->apk, L->lev, (uint32_t*)predT, ldp, bkt, bcnt, cap);
     } else if (pred16 == 2)
         lvl_pred_kernel<uint32_t><<<lvl_grid((const void*)lvl_pred_kernel<uint32_t>, L->nblk), 256, 0, st>>>(
             L->n, L->nw, L->nchunk, L->row0, L->nrows, L->D, L->nblk, L->off, L->arcs, L->aoff, L->ar,
