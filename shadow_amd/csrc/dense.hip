@@ -1968,8 +1968,8 @@ typedef struct {
     hipEvent_t kev[4];
     int kev_on;
     int diag_done; /* the level post pass applied the diagonal rule itself */
-    int pred16;    /* dt holds int16 predecessor rows (level post pass, n <= 32768; 2: packed
-                    * predecessor | reliability index words) */
+    int pred16;    /* what dt holds after the level post pass, as a srt_lvl_pred_layout: I16 rows
+                    * (n <= 32768), PK_COLS: packed predecessor | reliability index words */
     int pn_cap;    /* the level post pass took lvl_pred_near_kernel with this bucket capacity */
 } dense_ws;
 
@@ -2220,123 +2220,91 @@ static int dense_post(int32_t n, int32_t ld, int32_t row0, int32_t nrows, int32_
     return SRT_OK;
 }
 
+/* The post pass of a held level build: its predecessors (srt_levels_pred) into source-major rows in
+ * ws->dt, then the reliability pass over them, in the form the build was made for.
+ * Packed (SRT_LVL_POST_PK_*): one word per pair with the level, then rel_pk_kernel, which writes
+ * the u32 rows too: no u8 rows, no f64 slab. The words come straight from lvl_pred_rows_kernel (no
+ * predt slab, no transpose); with the tie count, or under SRT_FORM pkw=2, target-major from
+ * lvl_pred_kernel and through one u32 transpose.
+ * u8 rows (SRT_LVL_POST_U8): int16 predecessors while every vertex fits (half the slab's bytes),
+ * widened by the transpose into the int32 rows the reliability passes read; with the build's table
+ * of distinct arc reliabilities, one packed word per pair (predecessor | index << 16): 4 B written,
+ * transposed and read instead of 2 + 8. */
 static int dense_post_levels(int32_t n, int32_t ld, int32_t row0, int32_t nrows, uint32_t* d,
                              double* rel, hipStream_t st, srt_build_stats* stats, dense_ws* ws,
                              int lrows) {
     int rc;
-    if (lrows < nrows && srt_levels_pkw_ready()) { /* the padding rows of the last shard (or a
-        * shard past n): rel_pk_kernel writes the real rows only, so these take SRT_INF / 0 here,
-        * as lvl_out8_kernel's rows do on the other form */
+    const srt_lvl_post_form form = srt_levels_pkw_ready();
+    const bool packed = form != SRT_LVL_POST_U8;
+    if (lrows < nrows && packed) { /* the padding rows of the last shard (or a shard past n):
+        * rel_pk_kernel writes the real rows only, so these take SRT_INF / 0 here, as
+        * lvl_out8_kernel's rows do on the other form */
         SRT_HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d + (size_t)lrows * ld), (int)SRT_INF,
                                      (size_t)(nrows - lrows) * ld, st));
         SRT_HIPCHK(hipMemsetAsync(rel + (size_t)lrows * ld, 0, (size_t)(nrows - lrows) * ld * sizeof(double), st));
     }
-    if (lrows > 0 && srt_levels_pkw_ready()) {
-        /* the packed words with the level, source-major rows of stride ld in ws->dt, then
-         * rel_pk_kernel, which writes the u32 rows too: no u8 rows, no f64 slab. The words come
-         * straight from lvl_pred_rows_kernel (no predt slab, no transpose); with the tie count,
-         * or under SRT_FORM pkw=2, target-major from lvl_pred_kernel and through one u32
-         * transpose */
-        const size_t slab = (size_t)ld * nrows;
-        size_t c1 = ws->dt_cap;
-        if ((rc = ws_grow((void**)&ws->dt, &c1, slab, sizeof(uint32_t)))) return rc;
-        ws->dt_cap = c1;
+    if (lrows > 0) {
         const bool ties = stats && stats->count_ties;
-        if (ties) SRT_HIPCHK(hipMemsetAsync(ws->ties, 0, sizeof(unsigned long long), st));
-        const bool kt = stats && stats->time_kernels;
-        if (kt && !ws->kev[0])
-            for (int i = 0; i < 4; i++) SRT_HIPCHK(hipEventCreate(&ws->kev[i]));
         int ntab = 0;
-        const double* rtab = srt_levels_rtab(&ntab);
-        if (stats) stats->rel_table = ntab;
-        uint32_t* pk = reinterpret_cast<uint32_t*>(ws->dt);
-        if (kt) SRT_HIPCHK(hipEventRecord(ws->kev[0], st));
-        const bool rows = !ties && srt_levels_pkw_ready() == 1;
-        SRT_HIPCHK(hipMemsetAsync(ws->depth + 1, 0, sizeof(int32_t), st));
-        if (rows) {
-            if ((rc = srt_levels_pred(pk, 3, nullptr, (size_t)ld, NULL, ws->depth + 1, &ws->pn_cap, st)))
-                return rc;
-        } else { /* target-major packed words (with the level), then one u32 transpose */
-            size_t c2 = ws->predt_cap;
-            if ((rc = ws_grow((void**)&ws->predt, &c2, slab, sizeof(int32_t)))) return rc;
-            ws->predt_cap = c2;
-            if ((rc = srt_levels_pred(ws->predt, 2, nullptr, (size_t)nrows, ties ? ws->ties : NULL,
-                                      ws->depth + 1, &ws->pn_cap, st)))
-                return rc;
-        }
-        if (kt) SRT_HIPCHK(hipEventRecord(ws->kev[1], st));
-        if (!rows)
-            transpose_kernel<uint32_t><<<dim3(srt_ceil_div(nrows, 64), srt_ceil_div(n, 64)), 256, 0, st>>>(
-                n, nrows, reinterpret_cast<const uint32_t*>(ws->predt), (size_t)nrows, pk, (size_t)ld);
-        ws->pred16 = 2; /* dense_path_ms reads the packed words' low half */
-        SRT_HIPCHK(hipMemsetAsync(ws->depth, 0, sizeof(int32_t), st));
-        if (kt) SRT_HIPCHK(hipEventRecord(ws->kev[2], st));
-        if ((rc = rel_pk_launch(n, ld, row0, lrows, pk, d, rel, rtab, ntab, ws->depth, ws->cursor,
-                                st)))
-            return rc;
-        if (kt) {
-            SRT_HIPCHK(hipEventRecord(ws->kev[3], st));
-            ws->kev_on = 1;
-        }
-        if ((rc = srt_levels_diag(n, ld, d, rel, st, &ws->diag_done))) return rc;
-    } else if (lrows > 0) {
+        const double* rtab = n <= 32768 ? srt_levels_rtab(&ntab) : nullptr;
+        if (stats) stats->rel_table = rtab ? ntab : 0;
+        const srt_lvl_pred_layout out = packed ? (!ties && form == SRT_LVL_POST_PK_ROWS ? SRT_LVL_PRED_PK_ROWS
+                                                                                         : SRT_LVL_PRED_PK_COLS)
+                                        : rtab       ? SRT_LVL_PRED_PK_COLS
+                                        : n <= 32768 ? SRT_LVL_PRED_I16
+                                                     : SRT_LVL_PRED_I32;
+        const bool rows = out == SRT_LVL_PRED_PK_ROWS, pkw = out == SRT_LVL_PRED_PK_COLS || rows;
         const size_t slab = (size_t)ld * nrows;
         size_t c1 = ws->dt_cap, c2 = ws->predt_cap, c4 = ws->rt_cap;
         if ((rc = ws_grow((void**)&ws->dt, &c1, slab, sizeof(uint32_t)))) return rc;
         ws->dt_cap = c1;
-        if ((rc = ws_grow((void**)&ws->predt, &c2, slab, sizeof(int32_t)))) return rc;
+        if (!rows && (rc = ws_grow((void**)&ws->predt, &c2, slab, sizeof(int32_t)))) return rc;
         ws->predt_cap = c2;
-        if ((rc = ws_grow((void**)&ws->rt, &c4, slab, sizeof(double)))) return rc;
+        if (!packed && (rc = ws_grow((void**)&ws->rt, &c4, slab, sizeof(double)))) return rc;
         ws->rt_cap = c4;
-        const bool ties = stats && stats->count_ties;
         if (ties) SRT_HIPCHK(hipMemsetAsync(ws->ties, 0, sizeof(unsigned long long), st));
         const bool kt = stats && stats->time_kernels;
         if (kt && !ws->kev[0])
             for (int i = 0; i < 4; i++) SRT_HIPCHK(hipEventCreate(&ws->kev[i]));
         if (kt) SRT_HIPCHK(hipEventRecord(ws->kev[0], st));
-        /* int16 predecessors while every vertex fits (half the slab's bytes), widened by the
-         * transpose into the int32 rows the reliability passes read; with the build's table of
-         * distinct arc reliabilities, one packed word per pair (predecessor | index << 16): 4 B
-         * written, transposed and read instead of 2 + 8 */
-        int ntab = 0;
-        const double* rtab = n <= 32768 ? srt_levels_rtab(&ntab) : nullptr;
-        const int p16 = rtab ? 2 : n <= 32768;
-        if (stats) stats->rel_table = rtab ? ntab : 0;
         SRT_HIPCHK(hipMemsetAsync(ws->depth + 1, 0, sizeof(int32_t), st));
-        if ((rc = srt_levels_pred(ws->predt, p16, ws->rt, (size_t)nrows, ties ? ws->ties : NULL,
-                                  ws->depth + 1, &ws->pn_cap, st)))
+        if ((rc = srt_levels_pred(rows ? (void*)ws->dt : (void*)ws->predt, out, packed ? nullptr : ws->rt,
+                                  rows ? (size_t)ld : (size_t)nrows, ties ? ws->ties : NULL, ws->depth + 1,
+                                  &ws->pn_cap, st)))
             return rc;
         if (kt) SRT_HIPCHK(hipEventRecord(ws->kev[1], st));
-        int32_t* pred = reinterpret_cast<int32_t*>(ws->dt);
-        int16_t* pred16 = p16 == 1 ? reinterpret_cast<int16_t*>(ws->dt) : nullptr;
-        uint32_t* pk = p16 == 2 ? reinterpret_cast<uint32_t*>(ws->dt) : nullptr;
-        ws->pred16 = p16;
-        if (pk)
-            transpose_kernel<uint32_t><<<dim3(srt_ceil_div(nrows, 64), srt_ceil_div(n, 64)), 256, 0, st>>>(
-                n, nrows, reinterpret_cast<const uint32_t*>(ws->predt), (size_t)nrows, pk, (size_t)ld);
-        else if (p16) /* int16 rows: the reliability passes read them as they are */
-            transpose_kernel<int16_t><<<dim3(srt_ceil_div(nrows, 64), srt_ceil_div(n, 64)), 256, 0, st>>>(
-                n, nrows, reinterpret_cast<const int16_t*>(ws->predt), (size_t)nrows, pred16, (size_t)ld);
-        else
-            transpose_kernel<uint32_t><<<dim3(srt_ceil_div(nrows, 64), srt_ceil_div(n, 64)), 256, 0, st>>>(
-                n, nrows, reinterpret_cast<const uint32_t*>(ws->predt), (size_t)nrows,
-                reinterpret_cast<uint32_t*>(pred), (size_t)ld);
-        if (!pk)
-            transpose_kernel<double><<<dim3(srt_ceil_div(nrows, 64), srt_ceil_div(n, 64)), 256, 0, st>>>(
-                n, nrows, ws->rt, (size_t)nrows, rel, (size_t)ld);
+        /* the target-major slabs into rows of ws->dt (int16 rows: the reliability passes read them
+         * as they are) and of rel */
+        const dim3 tgrid(srt_ceil_div(nrows, 64), srt_ceil_div(n, 64));
+        if (out == SRT_LVL_PRED_I16)
+            transpose_kernel<int16_t><<<tgrid, 256, 0, st>>>(n, nrows, reinterpret_cast<const int16_t*>(ws->predt),
+                                                             (size_t)nrows, reinterpret_cast<int16_t*>(ws->dt),
+                                                             (size_t)ld);
+        else if (!rows)
+            transpose_kernel<uint32_t><<<tgrid, 256, 0, st>>>(n, nrows, reinterpret_cast<const uint32_t*>(ws->predt),
+                                                              (size_t)nrows, reinterpret_cast<uint32_t*>(ws->dt),
+                                                              (size_t)ld);
+        if (!pkw) transpose_kernel<double><<<tgrid, 256, 0, st>>>(n, nrows, ws->rt, (size_t)nrows, rel, (size_t)ld);
+        /* what ws->dt holds for dense_path_ms: int32, int16, or packed words (their low half) */
+        ws->pred16 = pkw ? (int)SRT_LVL_PRED_PK_COLS : (int)out;
         SRT_HIPCHK(hipMemsetAsync(ws->depth, 0, sizeof(int32_t), st));
-        /* every level-built distance is <= 254 quanta: level order in place for every row that
-         * spans <= 64 quanta, sweeps for the rest (as dense_post); the level rows as u8 */
         if (kt) SRT_HIPCHK(hipEventRecord(ws->kev[2], st));
-        if ((rc = rel_rows_launch(n, ld, row0, lrows, d, pred, rel, ws->depth, ws->cursor, nullptr,
-                                  st, srt_levels_l8(), pred16, pk, rtab, ntab)))
-            return rc;
+        if (packed)
+            rc = rel_pk_launch(n, ld, row0, lrows, reinterpret_cast<uint32_t*>(ws->dt), d, rel, rtab, ntab,
+                               ws->depth, ws->cursor, st);
+        else /* every level-built distance is <= 254 quanta: level order in place for every row that
+              * spans <= 64 quanta, sweeps for the rest (as dense_post); the level rows as u8 */
+            rc = rel_rows_launch(n, ld, row0, lrows, d, reinterpret_cast<int32_t*>(ws->dt), rel, ws->depth,
+                                 ws->cursor, nullptr, st, srt_levels_l8(),
+                                 out == SRT_LVL_PRED_I16 ? reinterpret_cast<int16_t*>(ws->dt) : nullptr,
+                                 pkw ? reinterpret_cast<uint32_t*>(ws->dt) : nullptr, rtab, ntab);
+        if (rc) return rc;
         if (kt) {
             SRT_HIPCHK(hipEventRecord(ws->kev[3], st));
             ws->kev_on = 1;
         }
-        /* the diagonal rule from the keys the level build's count pass took (no second read
-         * of the w rows); directed builds keep dense_diag_kernel */
+        /* the diagonal rule from the keys the level build's count pass took (no second read of the
+         * w rows); directed builds keep dense_diag_kernel */
         if ((rc = srt_levels_diag(n, ld, d, rel, st, &ws->diag_done))) return rc;
     }
     srt_levels_release(st);

@@ -1029,6 +1029,8 @@ static int lvl_side_stream(hipStream_t* cs, hipEvent_t** ev) {
 }
 /* the host-side set that deduplicates the exchanged reliability blocks, per slot */
 static std::vector<unsigned long long> g_lvl_uset[SRT_STATE_SLOTS];
+/* ... and their sorted union (lvl_union) */
+static std::vector<unsigned long long> g_lvl_union[SRT_STATE_SLOTS];
 /* The build's host round trips (the exchange, the agreement, one vote per batch) go through
  * pinned staging, per slot, made once and grown when a larger exchange needs it: a copy to or
  * from pageable memory is staged by the runtime and blocks the calling thread. Layout (u64
@@ -2168,8 +2170,9 @@ static unsigned lvl_grid(const void* fn, unsigned nblk, int reserve_cus = 0, int
 }
 
 /* The state a successful level build keeps for its post pass (srt_levels_pred), per state slot:
- * the sorted in-arcs with their reliabilities and the level planes. Freed by srt_levels_release
- * (stream-ordered). */
+ * the sorted in-arcs with their reliabilities and the level planes. The build (lvl_build) fills it
+ * in place and sets `held` last; until then the fields are the build's own (arcs, ar and total are
+ * its extraction cursor). Freed by srt_levels_release (stream-ordered). */
 typedef struct {
     int held;
     int n, nw, nchunk, row0, nrows, D;
@@ -2179,12 +2182,14 @@ typedef struct {
     uint32_t* aoff;
     double* ar;
     uint16_t* rix; /* packed form: each arc's index into rtab (NULL: more than LVL_RT_CAP values) */
-    uint32_t* apk; /* pkw 1: each arc's source | rix << 16 (lvl_apk_kernel) */
+    uint32_t* apk; /* source-major packed form: each arc's source | rix << 16 (lvl_apk_kernel) */
     double* rtab;
     int ntab;
     uint32_t* lev;
     uint8_t* l8; /* u8 distance rows (nrows x ld) for the reliability pass */
-    int pkw;     /* the post pass is the packed words with levels + rel_pk (no lat / l8 rows) */
+    srt_lvl_post_form post; /* the post pass: packed words with levels + rel_pk (no lat / l8 rows), or u8 */
+    int fpkw;    /* SRT_FORM pkw as the build read it: 3 / 4 force the narrow units' length */
+    int fbcap;   /* SRT_FORM bcap as the build read it: the pre-pass's bucket hook */
     int total;   /* in-arcs held (w <= lmax) */
     int pn_cap;  /* lvl_pred_near_kernel: the bucket capacity the weight histogram asks for */
     unsigned long long* dkey; /* the diagonal rule's key per local row (undirected rows form) */
@@ -2323,6 +2328,891 @@ __global__ void lvl_vote_kernel(const int* __restrict__ inc_last,
     vote[3] = (int32_t)(s >> 42);
 }
 
+/* u64 words of one rank's block of distinct reliabilities: two int32 flags (probe overflow, count),
+ * then up to LVL_RT_CAP values */
+constexpr size_t LVL_GB = LVL_RT_CAP + 1;
+/* wev[LVL_PREP]: the side stream's preparation (lvl_agree); wev[w]: weight w's arcs have arrived */
+#define LVL_PREP (LVL_BATCH + 1)
+
+/* What the phases of one srt_levels_build share. It lives on that function's stack and owns
+ * nothing: device memory belongs to the held state L (LVL_ALLOC), which the phases also fill in
+ * place -- L->off, aoff, lev, rix, rtab, dkey from the arenas, L->arcs / ar / total as the cursor
+ * of the current extraction, L->D and nblk from the levels. */
+struct lvl_build {
+    lvl_state* L;
+    /* the shape (dr: directed and N > 1; solo: a timing-only communicator) and the caller's rows */
+    int n, ld, row0, nrows, lrows, max_rows, nw, nchunk, R, me, fpkw;
+    bool directed, dr, solo;
+    size_t plane, ncnt, xn, dnt; /* words of a level plane, counts, exchange words, directed runs */
+    double fw_ms;
+    const srt_comm* comm;
+    hipStream_t st, wcs; /* wcs: the side stream, wev its events */
+    hipEvent_t* wev;
+    evpool_t* evp;
+    const uint32_t* w_rows;
+    const double* r_rows;
+    uint32_t* lat_rows;
+    /* the host-side words (LVL_H_*); dflag: [0] probe overflow, [1] distinct values */
+    unsigned long long* dhist;
+    int32_t *dinc, *dflag, *dagree, *dvote;
+    /* arena 1, the count pass (with L->off and L->dkey) */
+    int32_t *cnt, *tb, *xbuf, *scnt;
+    uint32_t* stash;
+    unsigned long long* H;
+    uint16_t *map, *cg;
+    /* arena 2, the extraction and the levels (with L->aoff, lev, rix, rtab); arena 3, the wire */
+    uint32_t *arcsA, *arcs2, *Rb, *wire;
+    double *arA, *ar2, *gat;
+    int32_t *seg, *packed, *tq, *oq, *dcur, *offw;
+    void *tmp, *stmp;
+    size_t tmp_bytes, sb;
+    uint8_t* done;
+    char* dwire;
+    /* pinned host views: the exchange, the agreement, the wire's bases, the union table + flags */
+    int32_t *hx, *hag, *hwt;
+    unsigned long long *pin, *ht;
+    unsigned long long hist[LVL_STRIDE]; /* summed over the ranks; [0] the stash overflows */
+    int32_t wmax[LVL_BATCH + 1];         /* undirected N > 1: the largest rank's arcs of weight w */
+    std::vector<unsigned long long>* u;  /* the union of the exchanged reliability blocks (per slot) */
+    /* this rank's plan, then the agreed values; the levels' outcome */
+    int failed, lx_own, lmax, lx, ok, stream_ok, all_done, hflag[2];
+    bool fit, want_rt, prepped;
+    int64_t gathered;
+    /* the extraction cursor (with L->arcs, ar, total): the weights the side stream delivers, their
+     * arcs carry table indices, the weights enqueued / placed so far, the directed ranks' counts */
+    int streamed, wnum, wq, wp;
+    lvl_dcnt dcn;
+};
+
+/* a group of buffers in one allocation (soft: a failure clears *okp) */
+static void lvl_commit(lvl_build& b, const lvl_arena& a, int* okp) {
+    lvl_state* const L = b.L;
+    const hipStream_t st = b.st;
+    char* base = NULL;
+    if (a.k) LVL_TRY_ALLOC(base, a.total(), okp);
+    if (base) a.carve(base);
+}
+
+/* the arcs of weight <= lw (global: the summed histogram) */
+static int64_t lvl_arcs_upto(const unsigned long long* hist, int lw) {
+    int64_t t = 0;
+    for (int x = 1; x <= lw; ++x) t += (int64_t)hist[x];
+    return t;
+}
+
+/* from the exchange: the largest rank's arcs of the weights w0..w1 (alike on every rank) */
+static uint64_t lvl_largest_block(const lvl_build& b, int w0, int w1) {
+    uint64_t mx = 0;
+    for (int q = 0; q < b.R; q++) {
+        uint64_t t = 0;
+        for (int w = w0; w <= w1; ++w) {
+            const int32_t* c = b.hx + LVL_X_LIMBS +
+                               (b.dr ? (size_t)q * LVL_X_DCNT + 2 * w : (size_t)q * LVL_X_CNT + 2 * (w - 1));
+            t += (uint32_t)c[0] | ((uint32_t)c[1] << 16);
+        }
+        mx = t > mx ? t : mx;
+    }
+    return mx;
+}
+/* directed, N > 1: arcs of the largest rank's block of the weights <= lw, made even */
+static size_t lvl_dblock(const lvl_build& b, int lw) { return (lvl_largest_block(b, 1, lw) + 1) & ~(uint64_t)1; }
+
+/* The sorted union of R reliability blocks (LVL_GB words each; only >= 0: that block stands for
+ * every rank, a solo rank's peers) into u: the same table on every rank. -> it can number the
+ * arcs: no probe overflow, 1..LVL_RT_CAP values. The blocks come in hash-slot order and mostly
+ * repeat each other (C4: ~500 values per rank, the same ones), so they are deduplicated through
+ * an open-addressing set first and only the distinct values sorted: sorting the concatenation
+ * (4,000 values at N = 8) cost ~0.1-0.2 ms of host time on the critical path. A solo rank's peers
+ * hold its own values (their rows are shifted copies of its rows), so it pays the same. */
+static bool lvl_union(const unsigned long long* blocks, int R, int only, std::vector<unsigned long long>& u) {
+    u.clear();
+    size_t all = 0;
+    for (int q = 0; q < R; q++) {
+        const int32_t* hd = reinterpret_cast<const int32_t*>(blocks + (size_t)(only >= 0 ? only : q) * LVL_GB);
+        if (hd[0] || hd[1] > LVL_RT_CAP) return false;
+        all += (size_t)max(hd[1], 0);
+    }
+    size_t cap = 64;
+    while (cap < 2 * all) cap <<= 1;
+    std::vector<unsigned long long>& set = g_lvl_uset[srt_state_slot()];
+    set.assign(cap, ~0ull); /* (a NaN pattern: never a reliability's bits) */
+    int shift = 64;
+    for (size_t c = cap; c > 1; c >>= 1) --shift;
+    for (int q = 0; q < R; q++) {
+        const unsigned long long* v = blocks + (size_t)(only >= 0 ? only : q) * LVL_GB;
+        const int nv = reinterpret_cast<const int32_t*>(v)[1];
+        for (int k = 1; k <= nv; ++k) {
+            size_t h = (size_t)((v[k] * 0x9E3779B97F4A7C15ull) >> shift);
+            while (set[h] != ~0ull && set[h] != v[k]) h = (h + 1) & (cap - 1);
+            if (set[h] == ~0ull) {
+                set[h] = v[k];
+                u.push_back(v[k]);
+            }
+        }
+    }
+    std::sort(u.begin(), u.end());
+    return !u.empty() && u.size() <= (size_t)LVL_RT_CAP;
+}
+
+/* Step 1: the count pass and, N > 1, this rank's slots of the exchange. Its buffers are taken
+ * softly: a rank short of memory sends every rank to the FW through the failure count it adds to
+ * the exchange (its slots stay zero). */
+static int lvl_count_pass(lvl_build& b) {
+    lvl_state* const L = b.L;
+    const hipStream_t st = b.st;
+    const int n = b.n, ld = b.ld, row0 = b.row0, nrows = b.nrows, lrows = b.lrows, R = b.R, me = b.me;
+    const size_t ncnt = b.ncnt;
+    LVL_ALLOC(b.dhist, LVL_H_WORDS * sizeof(unsigned long long));
+    SRT_HIPCHK(hipMemsetAsync(b.dhist, 0, LVL_H_WORDS * sizeof(unsigned long long), st));
+    b.dinc = reinterpret_cast<int*>(b.dhist + LVL_H_INC);
+    b.dagree = reinterpret_cast<int32_t*>(b.dhist + LVL_H_AGREE);
+    b.dvote = reinterpret_cast<int32_t*>(b.dhist + LVL_H_VOTE);
+    b.dflag = b.dinc + LVL_WMAX + 1;
+    lvl_arena a1;
+    a1.add(&b.cnt, (ncnt + 1) * sizeof(int32_t));
+    a1.add(&L->off, (ncnt + 1) * sizeof(int32_t));
+    a1.add(&b.tb, 2 * ((size_t)ld + 1) * sizeof(int32_t)); /* per-target totals, their scan */
+    a1.add(&b.H, LVL_RT_SLOTS * sizeof(unsigned long long));
+    a1.add(&b.map, LVL_RT_SLOTS * sizeof(uint16_t));
+    if (!b.directed) {
+        a1.add(&L->dkey, (size_t)nrows * sizeof(unsigned long long));
+        a1.add(&b.stash, (size_t)nrows * LVL_STASH_CAP * sizeof(uint32_t));
+        a1.add(&b.scnt, (size_t)nrows * 4 * sizeof(int32_t));
+    }
+    b.xn = b.dr ? lvl_xd_words(R) : R > 1 ? lvl_x_words(R) : 0;
+    if (R > 1) a1.add(&b.xbuf, b.xn * sizeof(int32_t));
+    lvl_commit(b, a1, &b.ok);
+    if (!b.ok) return SRT_OK;
+    int32_t* const cnt = b.cnt;
+    SRT_HIPCHK(hipMemsetAsync(cnt, 0, (ncnt + 1) * sizeof(int32_t), st));
+    if (b.dr) { /* this rank's rows' contribution to every target's counts */
+        if (lrows > 0)
+            lvl_arcs_colwin_kernel<false><<<dim3(ld / 64, srt_ceil_div(lrows, LVL_DROWS)), 256, 0, st>>>(
+                n, ld, row0, lrows, b.w_rows, cnt, 0);
+    } else if (b.directed)
+        lvl_arcs_cols_kernel<false><<<ld / 64, 256, 0, st>>>(n, ld, b.w_rows, cnt, 0, NULL, NULL);
+    else
+        lvl_arcs_rows_kernel<false><<<nrows, 256, 0, st>>>(n, ld, row0, b.w_rows, cnt, 0, NULL, NULL, NULL,
+                                                           NULL, L->dkey, b.stash, b.scnt, b.dhist);
+    if (b.solo && lrows > 0) lvl_solo_counts_kernel<<<n, 256, 0, st>>>(n, row0, nrows, lrows, cnt);
+    SRT_HIPCHK(hipGetLastError());
+    /* this rank's rows (a solo rank: every row of its synthesised counts, which are its own
+     * rows' n / lrows times over when that divides) */
+    const bool rep = b.solo && lrows > 0 && lrows == nrows && n % lrows == 0;
+    const bool own = R > 1 && !b.dr && (!b.solo || rep); /* (directed: every target's row) */
+    lvl_hist_kernel<<<own ? 256 : 1024, 256, 0, st>>>(own ? (size_t)(rep ? lrows : nrows) * LVL_STRIDE : ncnt,
+                                                     own ? cnt + (size_t)row0 * LVL_STRIDE : cnt, b.dhist,
+                                                     rep ? (unsigned)(n / lrows) : 1u);
+    SRT_HIPCHK(hipGetLastError());
+    if (R == 1) return SRT_OK;
+    int32_t* const xcnt = b.xbuf + LVL_X_LIMBS;
+    SRT_HIPCHK(hipMemsetAsync(b.xbuf, 0, b.xn * sizeof(int32_t), st));
+    lvl_hist_limbs_kernel<<<1, LVL_STRIDE, 0, st>>>(1, b.dhist, b.xbuf);
+    if (b.dr)
+        lvl_drank_counts_kernel<<<1, LVL_STRIDE, 0, st>>>(b.dhist, xcnt + (size_t)me * LVL_X_DCNT);
+    else
+        lvl_rank_counts_kernel<<<dim3(LVL_BATCH, b.solo ? R : 1), 256, 0, st>>>(n, ld, R, b.solo ? 0 : me, cnt, xcnt);
+    if (!b.directed && lrows > 0) { /* this rank's distinct light reliabilities, its block */
+        int32_t* hd = xcnt + (size_t)R * LVL_X_CNT + (size_t)me * LVL_GB * 2;
+        SRT_HIPCHK(hipMemsetAsync(b.H, 0xFF, LVL_RT_SLOTS * sizeof(unsigned long long), st));
+        /* the workgroup tables in the offsets' buffer (free until the offsets) */
+        size_t ntb = (ncnt + 1) * sizeof(int32_t) / (LVL_RT_LDS * sizeof(unsigned long long));
+        ntb = ntb < 512 ? ntb : 512;
+        ntb = ntb < (size_t)lrows ? ntb : (size_t)lrows;
+        const int nt = (int)(ntb > 0 ? ntb : 1);
+        unsigned long long* tabs = reinterpret_cast<unsigned long long*>(L->off);
+        lvl_rt_hash_stash_kernel<<<nt, 256, 0, st>>>(lrows, ld, LVL_BATCH, b.stash, b.scnt, b.r_rows, b.H, tabs,
+                                                     hd);
+        lvl_rt_merge_kernel<<<LVL_RT_LDS / 256 * srt_ceil_div(nt, LVL_RT_MC), 256, 0, st>>>(nt, tabs, b.H, hd);
+        lvl_rt_compact_kernel<<<1, 1024, 0, st>>>(b.H, b.map, reinterpret_cast<double*>(hd + 2), hd + 1);
+    }
+    SRT_HIPCHK(hipGetLastError());
+    return SRT_OK;
+}
+
+/* Step 1, second half: the exchange (one sum all-reduce) and its read-back, in pinned memory; the
+ * summed histogram, the failure count and, for the streamed wire, the largest rank's arcs per
+ * weight. One GPU: the histogram's read-back alone. */
+static int lvl_exchange(lvl_build& b) {
+    const hipStream_t st = b.st;
+    const int R = b.R;
+    const size_t xn = b.xn;
+    int rc;
+    if ((rc = lvl_pinned(LVL_PIN_X + (R > 1 ? (xn + 1) / 2 + LVL_RT_CAP + 2 * LVL_BATCH + 4 : 4), &b.pin)))
+        return rc;
+    b.hx = reinterpret_cast<int32_t*>(b.pin + LVL_PIN_X);
+    b.ht = b.pin + LVL_PIN_X + (xn + 1) / 2;
+    b.hwt = reinterpret_cast<int32_t*>(b.ht + LVL_RT_CAP + 2);
+    b.hag = reinterpret_cast<int32_t*>(b.pin + LVL_PIN_AG);
+    b.failed = !b.ok;
+    if (R > 1) {
+        b.hag[3] = b.failed;
+        SRT_HIPCHK(hipMemcpyAsync(b.xbuf + 2 * LVL_STRIDE, &b.hag[3], sizeof(int32_t), hipMemcpyHostToDevice, st));
+        if ((rc = srt_coll_allreduce_i32(b.comm, b.xbuf, xn, 0, st))) return rc;
+        SRT_HIPCHK(hipMemcpyAsync(b.hx, b.xbuf, xn * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    } else {
+        SRT_HIPCHK(hipMemcpyAsync(b.pin + LVL_PIN_HIST, b.dhist, sizeof(b.hist), hipMemcpyDeviceToHost, st));
+    }
+    if ((rc = lvl_wait(st))) return rc;
+    if (R == 1) {
+        memcpy(b.hist, b.pin + LVL_PIN_HIST, sizeof(b.hist));
+        return SRT_OK;
+    }
+    /* the summed histogram from its limbs, on the host (one read-back) */
+    b.failed = b.hx[2 * LVL_STRIDE];
+    for (int i = 0; i < LVL_STRIDE; i++)
+        b.hist[i] = (unsigned long long)(uint32_t)b.hx[i] + ((unsigned long long)(uint32_t)b.hx[LVL_STRIDE + i] << 20);
+    for (int w = 1; w <= LVL_BATCH && !b.dr; ++w) b.wmax[w] = (int32_t)lvl_largest_block(b, w, w);
+    return SRT_OK;
+}
+
+/* This rank's level budget, from global quantities (the summed histogram, the largest shard's
+ * words): the largest L whose predicted time stays under half the FW time; and by memory: the
+ * planes (L x n x nw words) within half of what the device has left. */
+static int lvl_own_budget(const lvl_build& b) {
+    int lmax = lvl_budget(b.hist, (double)b.n, (double)b.max_rows / 32.0, 0.5 * b.fw_ms);
+    if (b.plane > 0) {
+        const size_t cap = lvl_avail_bytes() / 2 / (b.plane * sizeof(uint32_t));
+        if ((size_t)lmax > cap) lmax = (int)cap;
+    }
+    if (b.R > 1) { /* test hook: this rank's memory stands in for a smaller budget (lcap_r<rank>) */
+        char key[32];
+        snprintf(key, sizeof(key), "lcap_r%d", b.me);
+        const int lc = srt_form_int(key, -1);
+        if (lc >= 0 && lc < lmax) lmax = lc;
+    }
+    return lmax;
+}
+
+/* Every allocation of the build up front, softly (b.ok), sized by THIS rank's budget b.lmax: the
+ * agreed budget is the ranks' minimum, so the buffers fit it. Then the streamed wire, where that
+ * form applies (b.stream_ok): step 2 agrees all three. */
+static int lvl_alloc_all(lvl_build& b) {
+    lvl_state* const L = b.L;
+    const hipStream_t st = b.st;
+    const int n = b.n, ld = b.ld, R = b.R;
+    const size_t ncnt = b.ncnt, plane = b.plane;
+    const int lmax_own = max(b.lmax, 0);
+    const int64_t total64 = lvl_arcs_upto(b.hist, lmax_own);
+    const int32_t total_own = (int32_t)(total64 < 0x7FFFFFF0ll ? total64 : 0x7FFFFFF0ll);
+    SRT_HIPCHK(hipcub::DeviceScan::ExclusiveSum(NULL, b.tmp_bytes, b.cnt, L->off, (int)(ncnt + 1), st));
+    b.dnt = (size_t)R * ((size_t)ld + 1) + 1; /* directed, N > 1: the runs' totals */
+    if (b.dr) {
+        size_t tb2 = 0;
+        SRT_HIPCHK(hipcub::DeviceScan::ExclusiveSum(NULL, tb2, b.cnt, L->off, (int)b.dnt, st));
+        b.tmp_bytes = max(b.tmp_bytes, tb2);
+    }
+    const bool need_sort_own = total_own > 0 && !(!b.directed && lmax_own <= LVL_STASH_W && b.hist[0] == 0);
+    if (need_sort_own)
+        SRT_HIPCHK(hipcub::DeviceSegmentedRadixSort::SortPairs(NULL, b.sb, b.arcsA, b.arcs2, b.arA, b.ar2,
+                                                               total_own, ld, b.seg, b.seg + 1, 0, 24, st));
+    lvl_arena a2;
+    if (total64 <= 0x7FFFFFF0ll && lmax_own >= 2) {
+        a2.add(&b.tmp, b.tmp_bytes);
+        a2.add(&b.arcsA, ((size_t)total_own + 8) * sizeof(uint32_t));
+        a2.add(&b.arA, ((size_t)total_own + 8) * sizeof(double));
+        if (need_sort_own) {
+            a2.add(&b.arcs2, ((size_t)total_own + 8) * sizeof(uint32_t));
+            a2.add(&b.ar2, ((size_t)total_own + 8) * sizeof(double));
+            a2.add(&b.seg, ((size_t)ld + 1) * sizeof(int32_t));
+            a2.add(&b.stmp, b.sb);
+        }
+        a2.add(&L->aoff, ((size_t)total_own + 64) * sizeof(uint32_t)); /* + a gather batch's tail */
+        a2.add(&L->lev, (size_t)lmax_own * plane * sizeof(uint32_t) + 16);
+        a2.add(&b.Rb, plane * sizeof(uint32_t) + 16);
+        a2.add(&b.done, (size_t)n * b.nchunk + 16);
+    }
+    /* the distinct arc reliabilities (packed post pass, n <= 32768) */
+    if (total_own > 0 && n <= 32768) {
+        a2.add(&L->rix, ((size_t)total_own + 8) * sizeof(uint16_t));
+        a2.add(&L->rtab, LVL_RT_CAP * sizeof(double));
+    }
+    /* N > 1: the segments' reliability blocks (lvl_bcast_segments), the counts' all-gather blocks
+     * (u16, every weight up to the budget), and the streamed wire's offsets at the shard starts */
+    if (total_own > 0 && n <= 32768 && R > 1 && !b.dr) a2.add(&b.gat, (size_t)R * LVL_GB * sizeof(double));
+    if (R > 1 && !b.dr) {
+        a2.add(&b.cg, ((size_t)R * b.max_rows * max(lmax_own, 1) + 8) * sizeof(uint16_t));
+        a2.add(&b.packed, (size_t)4 * LVL_BATCH * 65 * sizeof(int32_t));
+    }
+    /* directed, N > 1: every rank's (target, weight <= budget) counts, the runs' totals and their
+     * scan, the fill's cursors, and the gathered blocks of arcs (12 B per arc, every rank's block
+     * padded to the largest; the ranks' arcs per weight are in the exchange) */
+    if (b.dr) {
+        a2.add(&b.cg, ((size_t)R * ld * max(lmax_own, 1) + 8) * sizeof(uint16_t));
+        a2.add(&b.tq, b.dnt * sizeof(int32_t));
+        a2.add(&b.oq, b.dnt * sizeof(int32_t));
+        a2.add(&b.dcur, (ncnt + 1) * sizeof(int32_t));
+        a2.add(&b.dwire, (size_t)R * lvl_dblock(b, lmax_own) * 12 + 16);
+    }
+    lvl_commit(b, a2, &b.ok);
+    /* the streamed first extraction's wire (lvl_extract_streamed): every rank's block of a weight
+     * padded to the largest; needs the union table (fit) and at most 2 GB */
+    b.lx_own = min(lmax_own, LVL_BATCH);
+    size_t wire_words = 0;
+    for (int w = 1; w <= b.lx_own && R > 1; ++w) wire_words += (size_t)R * b.wmax[w];
+    b.stream_ok = R > 1 && !b.directed && b.hist[0] == 0 && b.fit && n <= 32768 && b.lx_own >= 1 &&
+                  b.fpkw != 0 && (double)wire_words * 4.0 < 2e9;
+    if (b.stream_ok && b.ok) {
+        int sok = 1;
+        lvl_arena a3;
+        a3.add(&b.offw, ((size_t)b.lx_own * ld + 1) * sizeof(int32_t));
+        /* (also the [weight][target] counts before their scan) */
+        a3.add(&b.wire, max(wire_words + 8, (size_t)b.lx_own * ld + 1) * sizeof(uint32_t));
+        lvl_commit(b, a3, &sok);
+        b.stream_ok = sok;
+    }
+    return SRT_OK;
+}
+
+/* Step 2: one min all-reduce agrees the budget, the allocation outcome and the wire. What needs
+ * no agreed value is done on the side stream while the main stream carries the agreement and the
+ * count all-gather (on the main stream it delayed them): the level state's zeroing and, for the
+ * streamed extraction, the union table and the wire's per-weight bases, sized by this rank's
+ * budget (lx_own >= the agreed lx; the entries of the weights up to lx are the same either way).
+ * The main stream waits for it (wev[LVL_PREP]) before the extraction; wasted when a rank falls
+ * back. */
+static int lvl_agree(lvl_build& b) {
+    lvl_state* const L = b.L;
+    const hipStream_t st = b.st;
+    const int R = b.R;
+    int rc;
+    if (R > 1 && b.ok && b.Rb && b.done) { /* (not allocated under a budget below 2) */
+        if ((rc = lvl_side_stream(&b.wcs, &b.wev))) return rc;
+        SRT_HIPCHK(hipEventRecord(b.wev[LVL_PREP], st)); /* the allocations are ordered on st */
+        SRT_HIPCHK(hipStreamWaitEvent(b.wcs, b.wev[LVL_PREP], 0));
+        b.prepped = true;
+    }
+    if (R > 1) { /* the agreement goes out first; the side stream's calls are made under it */
+        b.hag[0] = b.lmax;
+        b.hag[1] = b.ok;
+        b.hag[2] = b.stream_ok;
+        SRT_HIPCHK(hipMemcpyAsync(b.dagree, b.hag, 3 * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        if ((rc = srt_coll_allreduce_i32(b.comm, b.dagree, 3, 1, st))) return rc;
+        SRT_HIPCHK(hipMemcpyAsync(b.hag, b.dagree, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    }
+    if (b.prepped) {
+        SRT_HIPCHK(hipMemsetAsync(b.Rb, 0, b.plane * sizeof(uint32_t), b.wcs));
+        SRT_HIPCHK(hipMemsetAsync(b.done, 0, (size_t)b.n * b.nchunk, b.wcs));
+        lvl_init_kernel<<<srt_ceil_div(b.nrows, 256), 256, 0, b.wcs>>>(b.n, b.row0, b.nrows, b.nw, b.Rb);
+        SRT_HIPCHK(hipGetLastError());
+    }
+    if (b.prepped && b.stream_ok && L->lev && L->rtab) {
+        SRT_HIPCHK(hipMemsetAsync(L->lev, 0, (size_t)b.lx_own * b.plane * sizeof(uint32_t), b.wcs));
+        const int nu = (int)b.u->size();
+        memcpy(b.ht, b.u->data(), b.u->size() * sizeof(unsigned long long));
+        const int hf[2] = {0, nu};
+        memcpy(b.ht + LVL_RT_CAP, hf, sizeof(hf));
+        SRT_HIPCHK(hipMemcpyAsync(L->rtab, b.ht, (size_t)nu * sizeof(double), hipMemcpyHostToDevice, b.wcs));
+        SRT_HIPCHK(hipMemcpyAsync(b.dflag, b.ht + LVL_RT_CAP, 2 * sizeof(int), hipMemcpyHostToDevice, b.wcs));
+        /* the wire: per weight every rank's block padded to the largest rank's arcs: the weight's
+         * base and that block size */
+        size_t base = 0;
+        for (int w = 1; w <= b.lx_own; ++w) {
+            b.hwt[2 * (w - 1)] = (int32_t)base;
+            b.hwt[2 * (w - 1) + 1] = b.wmax[w];
+            base += (size_t)R * b.wmax[w];
+        }
+        SRT_HIPCHK(hipMemcpyAsync(b.packed + LVL_BATCH * 65, b.hwt, 2 * (size_t)b.lx_own * sizeof(int32_t),
+                                  hipMemcpyHostToDevice, b.wcs));
+    }
+    if (b.prepped) SRT_HIPCHK(hipEventRecord(b.wev[LVL_PREP], b.wcs));
+    if (R > 1) {
+        if ((rc = lvl_wait(st))) return rc;
+        b.lmax = b.hag[0];
+        b.ok = b.hag[1];
+        b.stream_ok = b.hag[2];
+    }
+    return SRT_OK;
+}
+
+/* Step 3, directed: every rank's contribution to every target's counts of the weights w0..w1, one
+ * all-gather of u16 blocks [weight][target]: summed into cnt, and kept per rank (dcn) for the
+ * placement */
+static int lvl_share_counts_directed(lvl_build& b, int w0, int w1) {
+    const hipStream_t st = b.st;
+    const int ld = b.ld, R = b.R;
+    const size_t dblk = (size_t)ld * (w1 - w0 + 1);
+    uint16_t* reg = b.cg + (size_t)R * ld * (w0 - 1); /* weights 1..lx, then lx + 1..lmax */
+    lvl_dcnt_pack_kernel<<<srt_ceil_div(ld, 256), 256, 0, st>>>(ld, w0, w1, b.cnt, reg + (size_t)b.me * dblk);
+    SRT_HIPCHK(hipGetLastError());
+    int rc = srt_coll_allgather(b.comm, reg, dblk * sizeof(uint16_t), st);
+    if (rc) return rc;
+    lvl_dcnt_sum_kernel<<<srt_ceil_div(ld, 256), 256, 0, st>>>(ld, R, w0, w1, reg, b.cnt);
+    SRT_HIPCHK(hipGetLastError());
+    if (w0 == 1) b.dcn = lvl_dcnt{reg, NULL, w1, w1, ld};
+    else b.dcn.b = reg, b.dcn.wb = w1;
+    return SRT_OK;
+}
+
+/* Step 3, undirected: every target's counts of the weights w0..w1 on every rank, one all-gather of
+ * the ranks' u16 blocks (a solo rank has them: synthesised) */
+static int lvl_share_counts_rows(lvl_build& b, int w0, int w1) {
+    const hipStream_t st = b.st;
+    const size_t blk = (size_t)b.max_rows * (w1 - w0 + 1);
+    if (b.nrows > 0)
+        lvl_cnt_gpack_kernel<<<srt_ceil_div(b.nrows, 256), 256, 0, st>>>(b.row0, b.nrows, b.max_rows, w0, w1, b.me,
+                                                                       b.cnt, b.cg);
+    SRT_HIPCHK(hipGetLastError());
+    int rc = srt_coll_allgather(b.comm, b.cg, blk * sizeof(uint16_t), st);
+    if (rc) return rc;
+    if (!b.solo)
+        lvl_cnt_gunpack_kernel<<<srt_ceil_div(b.ld, 256), 256, 0, st>>>(b.ld, b.R, b.max_rows, w0, w1, b.cg, b.cnt);
+    SRT_HIPCHK(hipGetLastError());
+    return SRT_OK;
+}
+
+static int lvl_share_counts(lvl_build& b, int w0, int w1) {
+    if (b.R == 1 || w1 < w0) return SRT_OK;
+    return b.dr ? lvl_share_counts_directed(b, w0, w1) : lvl_share_counts_rows(b, w0, w1);
+}
+
+/* Step 4: offsets of the (target, weight <= lw) in-arcs: narrow scan, counts untouched. ow, osz
+ * (the streamed form): the wire's offsets and their values at the shard starts. */
+static int lvl_offsets(lvl_build& b, int lw, int32_t* ow = NULL, int32_t* osz = NULL) {
+    const hipStream_t st = b.st;
+    const int ld = b.ld;
+    int32_t* const off = b.L->off;
+    if (lw <= LVL_BATCH) { /* a first extraction: two launches (with the wire's offsets) */
+        const int nb = (ld + 1 + 255) / 256; /* (the thread of target ld writes the totals) */
+        lvl_off_part_kernel<<<nb, 256, 0, st>>>(ld, lw, b.cnt, b.tb);
+        lvl_offsets_kernel<<<nb, 256, 0, st>>>(ld, lw, b.R, b.cnt, b.tb, off, ow, osz);
+        SRT_HIPCHK(hipGetLastError());
+        return SRT_OK;
+    }
+    lvl_tot_kernel<<<srt_ceil_div(ld + 1, 256), 256, 0, st>>>(ld, lw, b.cnt, b.tb);
+    SRT_HIPCHK(hipGetLastError());
+    SRT_HIPCHK(hipcub::DeviceScan::ExclusiveSum(b.tmp, b.tmp_bytes, b.tb, b.tb + ld + 1, ld + 1, st));
+    lvl_off_kernel<<<srt_ceil_div(ld + 1, 256), 256, 0, st>>>(ld, lw, b.cnt, b.tb + ld + 1, off);
+    SRT_HIPCHK(hipGetLastError());
+    return SRT_OK;
+}
+
+/* Step 4, directed, N > 1: this rank's arcs of weight <= lw into its block (12 B per arc), the
+ * blocks all-gathered once, then placed (lvl_dplace_kernel) */
+static int lvl_fill_directed_ranks(lvl_build& b, int lw) {
+    const hipStream_t st = b.st;
+    const int n = b.n, ld = b.ld, R = b.R;
+    const size_t blk = lvl_dblock(b, lw) * 12; /* (from the exchange: alike on every rank) */
+    lvl_dtot_kernel<<<(unsigned)((b.dnt + 255) / 256), 256, 0, st>>>(R, lw, b.dcn, b.tq);
+    SRT_HIPCHK(hipGetLastError());
+    SRT_HIPCHK(hipcub::DeviceScan::ExclusiveSum(b.tmp, b.tmp_bytes, b.tq, b.oq, (int)b.dnt, st));
+    lvl_dcur_kernel<<<srt_ceil_div(ld, 256), 256, 0, st>>>(b.me, lw, b.dcn, b.oq, b.dcur);
+    char* mine = b.dwire + (size_t)b.me * blk;
+    if (b.lrows > 0)
+        lvl_arcs_colwin_kernel<true><<<dim3(ld / 64, srt_ceil_div(b.lrows, LVL_DROWS)), 256, 0, st>>>(
+            n, ld, b.row0, b.lrows, b.w_rows, b.dcur, lw, reinterpret_cast<uint32_t*>(mine), b.r_rows,
+            reinterpret_cast<double*>(mine + blk / 3));
+    SRT_HIPCHK(hipGetLastError());
+    int rc = srt_coll_allgather(b.comm, b.dwire, blk, st);
+    if (rc) return rc;
+    lvl_dplace_kernel<<<srt_ceil_div(n, 4), 256, 0, st>>>(n, ld, R, blk, b.L->off, b.tq, b.oq, b.dwire, b.arcsA,
+                                                         b.arA);
+    SRT_HIPCHK(hipGetLastError());
+    return SRT_OK;
+}
+
+/* Step 4, every other form: this rank's arcs of weight <= lw into (target, weight)-major order,
+ * from the columns (directed, one GPU) or from its rows (undirected: its rows' segment) */
+static int lvl_fill_own(lvl_build& b, int lw) {
+    const hipStream_t st = b.st;
+    if (b.directed)
+        lvl_arcs_cols_kernel<true><<<b.ld / 64, 256, 0, st>>>(b.n, b.ld, b.w_rows, NULL, lw, b.L->off, b.arcsA,
+                                                              b.r_rows, b.arA);
+    else
+        lvl_arcs_rows_kernel<true><<<b.nrows, 256, 0, st>>>(b.n, b.ld, b.row0, b.w_rows, NULL, lw, b.L->off,
+                                                            b.arcsA, b.r_rows, b.arA, NULL, b.stash, b.scnt);
+    SRT_HIPCHK(hipGetLastError());
+    return SRT_OK;
+}
+
+/* Step 4, undirected N > 1, the broadcast form: every rank filled its rows' segment; one
+ * broadcast group sends the segments. *numbered: they travelled as arcs + table indices.
+ * Numbered segments: the packed post pass needs each arc's index into the table of distinct
+ * reliabilities, not its f64. Each rank numbers its own segment's values (hash + compact), the
+ * blocks are all-gathered (16 KB per rank), every rank takes the union sorted by value bits -- the
+ * same table everywhere -- and the segments travel as arcs + u16 indices: 6 B per arc instead of
+ * 12. Taken when the post pass will be the packed one (levels <= lw <= 31, pkw) and the fill needs
+ * no sort (the sort carries the f64s); more than LVL_RT_CAP values in the union (or a probe
+ * overflow) keeps the f64 segments, on every rank alike. */
+static int lvl_bcast_segments(lvl_build& b, int lw, int sorted_w, int* numbered) {
+    lvl_state* const L = b.L;
+    const hipStream_t st = b.st;
+    const int R = b.R, ld = b.ld;
+    int rc;
+    int32_t hoff[65];
+    for (int q = 0; q <= R; q++) {
+        int32_t s = ld, e = ld;
+        if (q < R) srt_shard_rows(ld, SRT_SHARD_ALIGN, R, q, &s, &e);
+        SRT_HIPCHK(hipMemcpyAsync(&hoff[q], L->off + (size_t)s * LVL_STRIDE, sizeof(int32_t),
+                                  hipMemcpyDeviceToHost, st));
+    }
+    if ((rc = lvl_wait(st))) return rc;
+    const int nb0 = hoff[b.me], nb1 = hoff[b.me + 1]; /* the arcs this process numbers: its segment */
+    if (b.gat && sorted_w && lw <= 31 && b.fpkw != 0) {
+        double* const mine = b.gat + b.me * LVL_GB;
+        SRT_HIPCHK(hipMemsetAsync(b.gat, 0, (size_t)R * LVL_GB * sizeof(double), st));
+        if (nb1 > nb0) {
+            SRT_HIPCHK(hipMemsetAsync(b.dflag, 0, 2 * sizeof(int), st));
+            SRT_HIPCHK(hipMemsetAsync(b.H, 0xFF, LVL_RT_SLOTS * sizeof(unsigned long long), st));
+            lvl_rt_hash_kernel<<<lvl_rt_grid(nb1 - nb0), 256, 0, st>>>(NULL, NULL, nb0, nb1, b.arA, b.H, L->rix,
+                                                                      b.dflag);
+            lvl_rt_compact_kernel<<<1, 1024, 0, st>>>(b.H, b.map, mine + 1, b.dflag + 1);
+            SRT_HIPCHK(hipGetLastError());
+            SRT_HIPCHK(hipMemcpyAsync(mine, b.dflag, 2 * sizeof(int), hipMemcpyDeviceToDevice, st));
+        }
+        if ((rc = srt_coll_allgather(b.comm, b.gat, LVL_GB * sizeof(double), st))) return rc;
+        std::vector<unsigned long long> hg((size_t)R * LVL_GB);
+        SRT_HIPCHK(hipMemcpyAsync(hg.data(), b.gat, hg.size() * sizeof(unsigned long long),
+                                  hipMemcpyDeviceToHost, st));
+        if ((rc = lvl_wait(st))) return rc;
+        std::vector<unsigned long long>& u = *b.u;
+        if (lvl_union(hg.data(), R, -1, u)) {
+            const int nu = (int)u.size(), hf[2] = {0, nu};
+            SRT_HIPCHK(hipMemcpyAsync(L->rtab, u.data(), u.size() * sizeof(double), hipMemcpyHostToDevice, st));
+            SRT_HIPCHK(hipMemcpyAsync(b.dflag, hf, sizeof(hf), hipMemcpyHostToDevice, st));
+            if (nb1 > nb0)
+                lvl_rt_index_kernel<<<srt_ceil_div(nb1 - nb0, 256), 256, 0, st>>>(
+                    nb1 - nb0, b.arA + nb0, reinterpret_cast<const unsigned long long*>(L->rtab), nu,
+                    L->rix + nb0);
+            SRT_HIPCHK(hipGetLastError());
+            if ((rc = lvl_wait(st))) return rc; /* hf leaves scope, u may be rewritten */
+            *numbered = 1;
+        }
+    }
+    rc = srt_coll_group_begin(b.comm);
+    for (int q = 0; q < R && !rc; q++)
+        if (hoff[q + 1] > hoff[q]) {
+            const size_t c = (size_t)(hoff[q + 1] - hoff[q]);
+            rc = srt_coll_bcast(b.comm, b.arcsA + hoff[q], c * sizeof(uint32_t), q, st);
+            if (!rc)
+                rc = *numbered ? srt_coll_bcast(b.comm, L->rix + hoff[q], c * sizeof(uint16_t), q, st)
+                               : srt_coll_bcast(b.comm, b.arA + hoff[q], c * sizeof(double), q, st);
+        }
+    const int rc2 = srt_coll_group_end(b.comm);
+    if (rc || rc2) return rc ? rc : rc2;
+    if (b.solo && b.lrows > 0) {
+        lvl_solo_arcs_kernel<<<srt_ceil_div(b.n, 4), 256, 0, st>>>(b.n, b.row0, b.nrows, b.lrows, 1, lw, b.nw,
+                                                                 L->off, b.arcsA, *numbered ? L->rix : NULL,
+                                                                 *numbered ? NULL : b.arA, NULL);
+        SRT_HIPCHK(hipGetLastError());
+    }
+    return SRT_OK;
+}
+
+/* Step 4, the broadcast form (and every one-GPU build): the in-arcs of weight <= lw, from arcsA /
+ * arA again (not from an earlier sort's output), into L->arcs / ar with their plane offsets and
+ * the reliability table */
+static int lvl_extract(lvl_build& b, int lw) {
+    lvl_state* const L = b.L;
+    const hipStream_t st = b.st;
+    const int ld = b.ld;
+    int numbered = 0, rc;
+    L->total = (int32_t)lvl_arcs_upto(b.hist, lw);
+    const int sorted_w = !b.directed && lw <= LVL_STASH_W && b.hist[0] == 0; /* global values */
+    if ((rc = lvl_offsets(b, lw))) return rc; /* (target, weight <= lw)-major */
+    if (b.dr) {
+        if ((rc = lvl_fill_directed_ranks(b, lw))) return rc;
+    } else {
+        if ((rc = lvl_fill_own(b, lw))) return rc;
+        if (b.R > 1 && (rc = lvl_bcast_segments(b, lw, sorted_w, &numbered))) return rc;
+    }
+    /* in-arcs of each target sorted by (weight, source vertex): the order the predecessor search
+     * walks them in (the full-row fill's atomics leave the order inside a weight arbitrary; the
+     * ordered stash fill needs no sort) */
+    L->arcs = b.arcsA;
+    L->ar = b.arA;
+    if (L->total > 0 && !sorted_w) {
+        lvl_segs_kernel<<<srt_ceil_div(ld + 1, 256), 256, 0, st>>>(ld, L->off, b.seg);
+        SRT_HIPCHK(hipGetLastError());
+        SRT_HIPCHK(hipcub::DeviceSegmentedRadixSort::SortPairs(b.stmp, b.sb, b.arcsA, b.arcs2, b.arA, b.ar2,
+                                                               L->total, ld, b.seg, b.seg + 1, 0, 24, st));
+        L->arcs = b.arcs2;
+        L->ar = b.ar2;
+    }
+    if (L->total > 0) {
+        lvl_aoff_kernel<<<srt_ceil_div(L->total, 256), 256, 0, st>>>(L->total, b.nw, L->arcs, L->aoff);
+        SRT_HIPCHK(hipGetLastError());
+    }
+    /* the reliability table: its flags are read with the levels' completion (no round trip) */
+    if (b.want_rt && L->total > 0 && !numbered) {
+        SRT_HIPCHK(hipMemsetAsync(b.dflag, 0, 2 * sizeof(int), st));
+        SRT_HIPCHK(hipMemsetAsync(b.H, 0xFF, LVL_RT_SLOTS * sizeof(unsigned long long), st));
+        lvl_rt_hash_kernel<<<lvl_rt_grid(L->total), 256, 0, st>>>(NULL, NULL, 0, L->total, L->ar, b.H, L->rix,
+                                                                 b.dflag);
+        lvl_rt_compact_kernel<<<1, 1024, 0, st>>>(b.H, b.map, L->rtab, b.dflag + 1);
+        lvl_rt_remap_kernel<<<srt_ceil_div(L->total, 256), 256, 0, st>>>(L->total, b.map, L->rix);
+        SRT_HIPCHK(hipGetLastError());
+    }
+    return SRT_OK;
+}
+
+/* Step 4, undirected N > 1, the streamed form of the first extraction: the arcs of weight <= lw
+ * travel weight by weight on the side stream (lvl_stream_weight, lvl_place_weight); level d then
+ * waits for wev[d - 1] only. Taken when the fill is the ordered stash and the reliabilities can be
+ * numbered from the exchange (stream_ok); otherwise lvl_extract. No host round trip: the union
+ * table and the wire's per-weight bases are on the device since the agreement. */
+static int lvl_extract_streamed(lvl_build& b, int lw) {
+    lvl_state* const L = b.L;
+    const hipStream_t st = b.st;
+    const int n = b.n, ld = b.ld, row0 = b.row0, nrows = b.nrows, lrows = b.lrows, nw = b.nw;
+    int rc;
+    L->total = (int32_t)lvl_arcs_upto(b.hist, lw);
+    /* offsets over the arcs with w <= lw, (target, weight)-major, and the wire's: offw, the
+     * [weight][target] scan of every target's counts (gathered), dsz its values at the shard
+     * starts */
+    int32_t* const dsz = b.packed;
+    const int32_t* dwt = b.packed + LVL_BATCH * 65;
+    if ((rc = lvl_offsets(b, lw, b.offw, dsz))) return rc;
+    lvl_arcs_rows_kernel<true><<<nrows, 256, 0, st>>>(n, ld, row0, b.w_rows, NULL, lw, L->off, b.arcsA, b.r_rows,
+                                                      b.arA, NULL, b.stash, b.scnt);
+    const int32_t* lo = L->off + (size_t)row0 * LVL_STRIDE;
+    const int32_t* hi = L->off + (size_t)(row0 + nrows) * LVL_STRIDE;
+    /* each own arc's row offset and its index into the union table */
+    lvl_own_index_kernel<<<512, 256, 0, st>>>(lo, hi, nw, b.arcsA, b.arA,
+                                              reinterpret_cast<const unsigned long long*>(L->rtab),
+                                              (int)b.u->size(), L->aoff, L->rix);
+    if (lrows > 0)
+        lvl_wire_pack_kernel<<<srt_ceil_div(lrows, 4), 256, 0, st>>>(ld, row0, lrows, lw, b.R, b.me, L->off, b.offw,
+                                                                    dsz, dwt, b.arcsA, L->rix, b.arA, b.wire, NULL);
+    SRT_HIPCHK(hipGetLastError());
+    SRT_HIPCHK(hipEventRecord(b.wev[0], st));
+    SRT_HIPCHK(hipStreamWaitEvent(b.wcs, b.wev[0], 0));
+    /* while weight 1 travels: the own sources' arcs into their planes (zeroed since the
+     * agreement) */
+    if (b.solo && lrows > 0)
+        lvl_solo_direct_kernel<<<srt_ceil_div(n, 4), 256, 0, st>>>(n, row0, nrows, lrows, nw, lw, b.plane, L->off,
+                                                                   b.arcsA, L->lev, b.Rb);
+    else if (!b.solo && lrows > 0)
+        lvl_direct_kernel<<<srt_ceil_div(lrows, 4), 256, 0, st>>>(row0, row0 + lrows, nw, lw, b.plane, L->off,
+                                                                 b.arcsA, L->lev, b.Rb);
+    SRT_HIPCHK(hipGetLastError());
+    b.wnum = 1;
+    L->arcs = b.arcsA;
+    L->ar = b.arA;
+    b.streamed = lw;
+    return SRT_OK;
+}
+
+/* Step 4, weight w of the streamed extraction on the side stream: the all-gather of the blocks.
+ * Enqueued just before level w, so the host's calls for weight w + 1 overlap the levels on the
+ * GPU. */
+static int lvl_stream_weight(lvl_build& b, int w) {
+    const size_t base = (size_t)b.hwt[2 * (w - 1)], mx = (size_t)b.hwt[2 * (w - 1) + 1];
+    int rc = srt_coll_allgather(b.comm, b.wire + base, mx * sizeof(uint32_t), b.wcs);
+    if (rc) return rc;
+    SRT_HIPCHK(hipEventRecord(b.wev[w], b.wcs));
+    return SRT_OK;
+}
+
+/* Step 4, weight w's placement (the solo rank synthesises its peers' arcs instead), on the main
+ * stream between two levels: the all-gather finished under the previous level, and the whole GPU
+ * places the arcs in ~12 us. On the side stream the placement got only the CUs the persistent
+ * level grid left free and ended with the level it ran beside (72-135 us per weight on one rank
+ * of N = 8), and the last weight's all-gather queued behind it. */
+static int lvl_place_weight(lvl_build& b, int w) {
+    lvl_state* const L = b.L;
+    const hipStream_t st = b.st;
+    const int32_t* dsz = b.packed;
+    const int32_t* dwt = b.packed + LVL_BATCH * 65;
+    SRT_HIPCHK(hipStreamWaitEvent(st, b.wev[w], 0));
+    if (b.solo && b.lrows > 0)
+        lvl_solo_arcs_kernel<<<srt_ceil_div(b.n, 4), 256, 0, st>>>(b.n, b.row0, b.nrows, b.lrows, w, w, b.nw, L->off,
+                                                                 L->arcs, b.wnum ? L->rix : NULL,
+                                                                 b.wnum ? NULL : L->ar, L->aoff);
+    else if (!b.solo)
+        lvl_wire_unpack_kernel<<<srt_ceil_div(b.n, 4), 256, 0, st>>>(b.n, b.ld, b.row0, b.nrows, w, b.nw, b.R, L->off,
+                                                                   b.offw, dsz, dwt, b.wire, NULL, L->arcs, L->rix,
+                                                                   L->ar, L->aoff);
+    SRT_HIPCHK(hipGetLastError());
+    return SRT_OK;
+}
+
+/* Step 5, level d of a batch ending at d1 on the main stream, between two kernel-time events:
+ * first the streamed weights it is due (sent one ahead) and needs (placed) */
+static int lvl_level(lvl_build& b, int d, int d1, unsigned pgrid) {
+    lvl_state* const L = b.L;
+    const hipStream_t st = b.st;
+    evpool_t* const evp = b.evp;
+    const int n = b.n, nw = b.nw;
+    int rc;
+    /* weights go out one ahead of the levels (every rank alike: a settled rank still sends its
+     * arcs), but not past the batch they are for: a weight nobody's level needs is never sent (C4
+     * ends at level 5) */
+    while (b.wq < min(b.streamed, min(d + 1, d1)))
+        if ((rc = lvl_stream_weight(b, ++b.wq))) return rc;
+    if (L->D && d > L->D) return SRT_OK; /* this rank's sources are settled: nothing to run */
+    /* Level d reads the arcs of weight < d only: an arc of weight d counts for its own source
+     * alone (Delta_0), and lvl_direct_kernel put those into the planes from this rank's rows. So
+     * level d waits for weight d - 1, and level 1 for nothing. */
+    while (b.wp < min(d - 1, b.wq))
+        if ((rc = lvl_place_weight(b, ++b.wp))) return rc;
+    if (evp) SRT_HIPCHK(hipEventRecord(evp->ev[evp->used++], st));
+    if (d == 1) { /* the weight-1 arcs as bits; level 2 takes up the completion flags (dinc[1]
+                   * stays set: a graph settled at level 1 reports 2 levels). Streamed:
+                   * lvl_direct_kernel has set them. */
+        SRT_HIPCHK(hipMemsetAsync(b.dinc + 1, 0xFF, sizeof(int), st));
+        if (!b.streamed) {
+            SRT_HIPCHK(hipMemsetAsync(L->lev, 0, b.plane * sizeof(uint32_t), st));
+            lvl_first_kernel<<<srt_ceil_div(n, 4), 256, 0, st>>>(n, nw, b.row0, b.nrows, L->off, L->arcs, L->lev,
+                                                                  b.Rb);
+        }
+    } else {
+        /* levels 2 and 3: the weight-d and weight-(d - 1) groups from the in-arc runs
+         * (lvl_near_kernel); later levels stop after their first group almost everywhere (the
+         * early exit), so they keep the gathers. The runs are read whole for every target
+         * whatever a rank's share of the sources, so they pay only for a wide share (C4: 14.5 ->
+         * 14.1 ms on one GPU; a rank of N = 8, 128 words, went 2.55 -> 2.86 ms) */
+        const bool near = d <= 3 && d <= b.lx && nw >= LVL_NEAR_MIN_NW && nw <= LVL_NEAR_NW;
+        unsigned long long* nset = reinterpret_cast<unsigned long long*>(b.dagree + 4);
+        if (near)
+            lvl_near_kernel<<<srt_ceil_div(n, 4), 256, 4 * (size_t)nw * sizeof(uint32_t), st>>>(
+                d, n, nw, b.row0, b.nrows, d <= b.streamed, L->off, L->arcs, L->lev);
+        lvl_step_kernel<<<pgrid, 256, 0, st>>>(d, near ? 2 : d <= b.streamed, n, nw, b.nchunk, b.row0, b.nrows,
+                                              L->nblk, L->off, L->arcs, L->aoff, L->lev, b.Rb, b.done,
+                                              b.dinc + d, b.dinc + d - 1, nset, nset + 1);
+    }
+    if (evp) SRT_HIPCHK(hipEventRecord(evp->ev[evp->used++], st));
+    return SRT_OK;
+}
+
+/* Step 5, the end of the batch d0..d1: its weights in place, the vote (N > 1, one sum
+ * all-reduce) and the one read-back. Sets L->D (this rank's last level), b.all_done (the verdict)
+ * and *settled (the pairs settled at levels >= 2: over all ranks from the vote). */
+static int lvl_batch_end(lvl_build& b, int d0, int d1, unsigned long long* settled) {
+    lvl_state* const L = b.L;
+    const hipStream_t st = b.st;
+    int rc;
+    /* the batch's weights in place before anything after its levels (the post pass reads every
+     * arc up to the last level) */
+    while (b.wp < b.wq)
+        if ((rc = lvl_place_weight(b, ++b.wp))) return rc;
+    if (b.R > 1) {
+        lvl_vote_kernel<<<1, 64, 0, st>>>(b.dinc + d1, reinterpret_cast<unsigned long long*>(b.dagree + 4), b.dvote);
+        SRT_HIPCHK(hipGetLastError());
+        if ((rc = srt_coll_allreduce_i32(b.comm, b.dvote, 4, 0, st))) return rc;
+    }
+    /* one read-back: the completion flags, the table flags, the settled pairs, the gathered bytes
+     * and the vote are neighbours in the host-side words (four copies cost ~20 us each of round
+     * trip) */
+    unsigned long long* const hw = b.pin + LVL_PIN_HW;
+    SRT_HIPCHK(hipMemcpyAsync(hw, b.dhist + LVL_H_INC, (LVL_H_WORDS - LVL_H_INC) * sizeof(unsigned long long),
+                              hipMemcpyDeviceToHost, st));
+    if ((rc = lvl_wait(st))) return rc;
+    const int* hinc = reinterpret_cast<const int*>(hw);
+    const int32_t* vote = reinterpret_cast<const int32_t*>(hw + (LVL_H_VOTE - LVL_H_INC));
+    b.hflag[0] = hinc[LVL_WMAX + 1];
+    b.hflag[1] = hinc[LVL_WMAX + 2];
+    for (int d = d0; d <= d1 && !L->D; ++d)
+        if (hinc[d] == 0) L->D = d;
+    if (b.R > 1) {
+        b.all_done = vote[0] == 0;
+        *settled = (unsigned long long)(uint32_t)vote[1] + ((unsigned long long)(uint32_t)vote[2] << 21) +
+                   ((unsigned long long)(uint32_t)vote[3] << 42);
+    } else {
+        b.all_done = L->D != 0;
+        *settled = hw[LVL_H_AGREE + 2 - LVL_H_INC];
+    }
+    return SRT_OK;
+}
+
+/* Step 5: the levels in batches, one host round trip per batch. After the first batch the settled
+ * fraction decides whether the rest is worth it: a graph with far-apart vertices (metric
+ * latencies, C4metric: 0.2% settled after 8 levels, distances of hundreds of quanta) goes to the
+ * FW at once instead of spending its whole budget first (77 ms there). At N > 1 the decision is
+ * taken from the summed vote (lvl_vote_kernel): the fraction of all n^2 pairs, the same number on
+ * every rank and the one a single GPU would see. A rank whose own sources settled early runs the
+ * later levels as no-ops (lvl_step_kernel's prev test) and keeps its D. */
+static int lvl_levels(lvl_build& b) {
+    lvl_state* const L = b.L;
+    evpool_t* const evp = b.evp;
+    const int lmax = b.lmax, lx = b.lx;
+    int rc;
+    L->nblk = ((unsigned)(((b.n + 3) / 4) * b.nchunk) + 7u) & ~7u;
+    /* while the streamed arcs are still arriving, one CU per XCD stays free for the broadcast
+     * (RCCL's kernels, the unpack) beside the persistent level grid */
+    const unsigned pgrid = lvl_grid((const void*)lvl_step_kernel, L->nblk, b.streamed ? 8 : 0);
+    const int ev0 = evp ? evp->used : 0;
+    if (evp && (rc = evpool_reserve(evp, ev0 + 2 * lmax))) return rc;
+    for (int d0 = 1, d1 = 0; d0 <= lmax; d0 = d1 + 1) {
+        /* batches: levels 1-5 (C4's distances end at 4-5), then one level at a time up to
+         * LVL_BATCH (a level nobody needs is never launched, nor its weight waited for), then
+         * LVL_BATCH at a time */
+        d1 = d0 == 1 ? min(lmax, LVL_B1) : d0 <= LVL_BATCH ? d0 : min(lmax, d0 + LVL_BATCH - 1);
+        for (int d = d0; d <= d1; ++d)
+            if ((rc = lvl_level(b, d, d1, pgrid))) return rc;
+        SRT_HIPCHK(hipGetLastError());
+        unsigned long long settled = 0;
+        if ((rc = lvl_batch_end(b, d0, d1, &settled))) return rc;
+        if (b.all_done) break;
+        /* settled pairs of all sources: the levels >= 2 counted by lvl_step_kernel, every source's
+         * own vertex (level 0) and the weight-1 arcs (level 1, lvl_first_kernel counts none) */
+        const double frac = ((double)settled + (double)b.n + (double)b.hist[1]) / ((double)b.n * (double)b.n);
+        /* at the end of the first LVL_BATCH levels (a forced level build, fw_ms = 1e30 from
+         * SRT_FORM levels=1, runs its whole budget) */
+        if (d1 == lx && d1 < lmax && frac < LVL_MIN_SETTLED && b.fw_ms < 1e29)
+            break; /* -> Floyd-Warshall, every rank */
+        if (d1 == lx && lx < lmax) { /* the heavier arcs: their counts, then every arc up to lmax */
+            while (b.wq < b.streamed) /* (the first extraction's last weights, for the collectives) */
+                if ((rc = lvl_stream_weight(b, ++b.wq))) return rc;
+            while (b.wp < b.wq) /* its writes come first */
+                if ((rc = lvl_place_weight(b, ++b.wp))) return rc;
+            if ((rc = lvl_share_counts(b, lx + 1, lmax)) || (rc = lvl_extract(b, lmax))) return rc;
+        }
+    }
+    /* the side stream's last weight before anything frees the wire (lvl_free waits for it too) */
+    if (b.wq) L->wlast = b.wev[b.wq];
+    if (evp && L->D) evp->used = ev0 + 2 * L->D; /* the levels that did work */
+    /* the bytes the level kernels gathered, counted on the device (the early exit skips the later
+     * weight groups of a unit, so the model -- every arc of weight < d for every level -- would
+     * overstate them): dhist word 515, in the last batch's read-back */
+    b.gathered = (int64_t)(b.pin + LVL_PIN_HW)[LVL_H_AGREE + 3 - LVL_H_INC];
+    return SRT_OK;
+}
+
+/* The choice of the post pass and the hand-over: the build is held for srt_levels_pred.
+ * Source-major packed words (SRT_FORM pkw=1, the default; 3, 4: the same with srt_levels_pred's
+ * units forced to one sub-chunk, to whole chunks) where the arcs are numbered, at most 31 levels
+ * and u16 vertices: lvl_pred_rows_kernel's words with the level, then rel_pk_kernel, which writes
+ * the u32 rows too. pkw=2: lvl_pred_kernel's target-major words and one transpose before
+ * rel_pk_kernel. Past the packed form, or pkw=0: lvl_out8 rows + the predecessor rows +
+ * rel_tree_kernel. */
+static int lvl_hand_over(lvl_build& b, int* levels, int64_t* gather_bytes) {
+    lvl_state* const L = b.L;
+    const hipStream_t st = b.st;
+    const int D = L->D;
+    if (b.want_rt && !b.hflag[0] && b.hflag[1] <= LVL_RT_CAP)
+        L->ntab = b.hflag[1];
+    else
+        L->rix = NULL, L->rtab = NULL; /* (freed with the state) */
+    L->post = !L->rix || D > 31 || b.n > 32768 || b.fpkw == 0 ? SRT_LVL_POST_U8
+              : b.fpkw == 2                                    ? SRT_LVL_POST_PK_COLS
+                                                               : SRT_LVL_POST_PK_ROWS;
+    if (L->post == SRT_LVL_POST_PK_ROWS && L->total > 0) { /* 4 B per held arc (34 MB on C4) */
+        LVL_ALLOC(L->apk, (size_t)L->total * sizeof(uint32_t));
+        lvl_apk_kernel<<<srt_ceil_div(L->total, 256), 256, 0, st>>>(L->total, L->arcs, L->rix, L->apk);
+        SRT_HIPCHK(hipGetLastError());
+    }
+    if (L->post == SRT_LVL_POST_U8) {
+        LVL_ALLOC(L->l8, (size_t)b.nrows * b.ld);
+        if (D <= LVL_OUT_L) {
+            const int lds = D * 2 * 256 * (int)sizeof(uint4);
+            SRT_HIPCHK(hipFuncSetAttribute((const void*)lvl_out8_kernel,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+            lvl_out8_kernel<<<dim3(srt_ceil_div(b.ld, 256), srt_ceil_div(b.nw, 8)), 256, lds, st>>>(
+                b.n, b.ld, b.nw, b.row0, D, L->lev, b.lat_rows, L->l8);
+        } else {
+            lvl_out_kernel<<<dim3(srt_ceil_div(b.ld, 1024), srt_ceil_div(b.nw, 16)), 256, 0, st>>>(
+                b.n, b.ld, b.nw, b.row0, D, L->lev, b.lat_rows, L->l8);
+        }
+        SRT_HIPCHK(hipGetLastError());
+    }
+    L->pn_cap = lvl_pn_cap(b.hist, b.n, b.nrows, D);
+    *levels = D;
+    *gather_bytes = b.gathered;
+    L->held = 1;
+    return SRT_OK;
+}
+
 /* One build of the local rows' distances (nrows x ld). comm (NULL on one GPU): row
  * shards, every rank sees every target's in-arcs after the segment broadcasts (undirected) or the
  * all-gather of the ranks' blocks (directed). fw_ms: the
@@ -2336,19 +3226,19 @@ __global__ void lvl_vote_kernel(const int* __restrict__ inc_last,
  * The N > 1 protocol. Every branch after the first collective is taken on values every rank holds
  * alike -- the exchanged histogram and blocks, the agreed budget, allocation outcome and wire, and
  * each batch's summed vote -- so every rank makes the same collective calls in the same order and
- * no rank leaves while its peers wait in one. In order:
+ * no rank leaves while its peers wait in one. In order (each step's functions cite its number):
  *   1. one sum all-reduce of the exchange (lvl_x_words): the histogram limbs, the allocation-
  *      failure count, every rank's arcs per weight w <= LVL_BATCH, every rank's distinct light
  *      reliabilities (so the union table and the wire's block sizes need no later round trip);
  *   2. one min all-reduce of (budget, allocation outcome, wire allocated) -- each rank allocated
  *      for its own budget, which is at least the agreed one;
  *   3. the (target, weight <= lmax) counts (sum);
- *   4. the first batch's arcs: streamed, one all-gather per weight w <= lx (every rank's block
- *      padded to the largest), sent one weight ahead of the levels on the side stream; or, where
- *      that form does not apply, extract(): the reliability blocks' all-gather and one broadcast
- *      group of the segments;
+ *   4. the first batch's arcs: streamed (lvl_extract_streamed), one all-gather per weight w <= lx
+ *      (every rank's block padded to the largest), sent one weight ahead of the levels on the side
+ *      stream; or, where that form does not apply, lvl_extract: the reliability blocks' all-gather
+ *      and one broadcast group of the segments (lvl_bcast_segments);
  *   5. per batch of levels (1-5, then 6, 7, 8 one at a time, then 8 at a time) the vote
- *      (sum); after the batch ending at lx < lmax, extract(lmax) as in 4's second form.
+ *      (sum); after the batch ending at lx < lmax, lvl_extract(lmax) as in 4's second form.
  * The vote's "all done" is the verdict. tests/test_dist_gloo.py rehearses this sequence over gloo
  * and tests/test_gpu_protocol.py checks every rank's collective log (srt_comm_log_*) against it.
  *
@@ -2382,21 +3272,34 @@ int srt_levels_build(const srt_comm* comm, int n, int ld, int row0, int nrows, i
     if (n > 65535 || ld % 128 || nrows % 128 || row0 % 128 || R > 64) return SRT_OK;
     /* directed, N > 1: the extraction of the header's "directed graph, N > 1" section; a
      * timing-only communicator has no synthesis for it and keeps the FW (before any collective) */
-    const bool dr = R > 1 && directed;
-    if (dr && srt_comm_is_solo(comm)) return SRT_OK;
+    if (R > 1 && directed && srt_comm_is_solo(comm)) return SRT_OK;
     int max_rows = nrows;
     for (int q = 0; q < R && R > 1; q++) {
-        int32_t b = 0, e = 0;
-        srt_shard_rows(ld, SRT_SHARD_ALIGN, R, q, &b, &e);
-        max_rows = max(max_rows, e - b);
+        int32_t s = 0, e = 0;
+        srt_shard_rows(ld, SRT_SHARD_ALIGN, R, q, &s, &e);
+        max_rows = max(max_rows, e - s);
     }
     if ((size_t)n * (size_t)(max_rows / 32) * 4 > 0xFFFFFFFFull) return SRT_OK; /* 32-bit offsets */
-    const int nw = nrows / 32, nchunk = (nw + 63) / 64;
+    lvl_build b{};
+    b.L = L, b.comm = comm, b.st = st, b.evp = evp;
+    b.w_rows = w_rows, b.r_rows = r_rows, b.lat_rows = lat_rows, b.fw_ms = fw_ms;
+    b.n = n, b.ld = ld, b.row0 = row0, b.nrows = nrows, b.max_rows = max_rows, b.R = R;
+    b.nw = nrows / 32, b.nchunk = (b.nw + 63) / 64, b.plane = (size_t)n * b.nw;
+    b.lrows = min(nrows, max(0, n - row0));
+    b.ncnt = (size_t)ld * LVL_STRIDE;
+    b.directed = directed != 0, b.dr = R > 1 && directed;
     /* a timing-only communicator (srt_comm_init_solo*, tools/solo_rank.py): the rank does a real
      * rank's work on its own rows and synthesises what its peers would send (lvl_solo_*) */
-    const bool solo = R > 1 && srt_comm_is_solo(comm);
-    const int lrows = min(nrows, max(0, n - row0));
-    L->st = st;
+    b.solo = R > 1 && srt_comm_is_solo(comm);
+    b.me = R > 1 ? srt_comm_rank(comm) : 0;
+    b.dcn.ld = ld;
+    b.u = &g_lvl_union[srt_state_slot()];
+    b.ok = 1;
+    /* SRT_FORM pkw and bcap are read here alone; the post pass takes them from the held state */
+    b.fpkw = L->fpkw = srt_form_int("pkw", 1);
+    L->fbcap = srt_form_int("bcap", 0);
+    L->st = st, L->n = n, L->nw = b.nw, L->nchunk = b.nchunk, L->row0 = row0, L->nrows = nrows;
+    L->r_rows = r_rows;
     /* on any early return below the allocations go back (lvl_free), unless the build is held */
     struct guard {
         lvl_state* L;
@@ -2405,835 +3308,70 @@ int srt_levels_build(const srt_comm* comm, int n, int ld, int row0, int nrows, i
             if (!L->held) lvl_free(L, st);
         }
     } gd{L, st};
-    const size_t ncnt = (size_t)ld * LVL_STRIDE;
-    unsigned long long* dhist = NULL; /* the host-side words (LVL_H_*), a few KB */
-    LVL_ALLOC(dhist, LVL_H_WORDS * sizeof(unsigned long long));
-    SRT_HIPCHK(hipMemsetAsync(dhist, 0, LVL_H_WORDS * sizeof(unsigned long long), st));
-    int* dinc = reinterpret_cast<int*>(dhist + LVL_H_INC);
-    int32_t* dagree = reinterpret_cast<int32_t*>(dhist + LVL_H_AGREE);
-    int32_t* dvote = reinterpret_cast<int32_t*>(dhist + LVL_H_VOTE);
-    int* dflag = dinc + LVL_WMAX + 1; /* [0] probe overflow, [1] distinct values */
-    const int me = R > 1 ? srt_comm_rank(comm) : 0;
-    /* the count pass's buffers, softly: a rank short of memory sends every rank to the FW through
-     * the failure count it adds to the exchange (its slots stay zero) */
-    int ok = 1;
-    int32_t *cnt = NULL, *off = NULL, *tb = NULL, *xbuf = NULL;
-    unsigned long long* dkey = NULL;
-    uint32_t* stash = NULL;
-    int32_t* scnt = NULL;
-    unsigned long long* H = NULL;
-    uint16_t* map = NULL;
-    /* a group of buffers in one allocation (soft: a failure clears *okp) */
-    auto commit = [&](const lvl_arena& a, int* okp) {
-        char* base = NULL;
-        if (a.k) LVL_TRY_ALLOC(base, a.total(), okp);
-        if (base) a.carve(base);
-    };
-    lvl_arena a1;
-    a1.add(&cnt, (ncnt + 1) * sizeof(int32_t));
-    a1.add(&off, (ncnt + 1) * sizeof(int32_t));
-    a1.add(&tb, 2 * ((size_t)ld + 1) * sizeof(int32_t)); /* per-target totals, their scan */
-    a1.add(&H, LVL_RT_SLOTS * sizeof(unsigned long long));
-    a1.add(&map, LVL_RT_SLOTS * sizeof(uint16_t));
-    if (!directed) {
-        a1.add(&dkey, (size_t)nrows * sizeof(unsigned long long));
-        a1.add(&stash, (size_t)nrows * LVL_STASH_CAP * sizeof(uint32_t));
-        a1.add(&scnt, (size_t)nrows * 4 * sizeof(int32_t));
-    }
-    const size_t xn = dr ? lvl_xd_words(R) : R > 1 ? lvl_x_words(R) : 0;
-    if (R > 1) a1.add(&xbuf, xn * sizeof(int32_t));
-    commit(a1, &ok);
-    constexpr size_t LVL_GB = LVL_RT_CAP + 1;
-    int32_t* const xlimbs = xbuf;
-    int32_t* const xcnt = xbuf ? xbuf + LVL_X_LIMBS : NULL;
-    int32_t* const xblk = xbuf ? xcnt + (size_t)R * LVL_X_CNT : NULL; /* R blocks of LVL_GB u64 */
-    if (ok) {
-        SRT_HIPCHK(hipMemsetAsync(cnt, 0, (ncnt + 1) * sizeof(int32_t), st));
-        if (dr) { /* this rank's rows' contribution to every target's counts */
-            if (lrows > 0)
-                lvl_arcs_colwin_kernel<false><<<dim3(ld / 64, srt_ceil_div(lrows, LVL_DROWS)), 256, 0, st>>>(
-                    n, ld, row0, lrows, w_rows, cnt, 0);
-        } else if (directed)
-            lvl_arcs_cols_kernel<false><<<ld / 64, 256, 0, st>>>(n, ld, w_rows, cnt, 0, NULL, NULL);
-        else
-            lvl_arcs_rows_kernel<false><<<nrows, 256, 0, st>>>(n, ld, row0, w_rows, cnt, 0, NULL, NULL,
-                                                               NULL, NULL, dkey, stash, scnt, dhist);
-        if (solo && lrows > 0) lvl_solo_counts_kernel<<<n, 256, 0, st>>>(n, row0, nrows, lrows, cnt);
-        SRT_HIPCHK(hipGetLastError());
-        /* this rank's rows (a solo rank: every row of its synthesised counts, which are its own
-         * rows' n / lrows times over when that divides) */
-        const bool rep = solo && lrows > 0 && lrows == nrows && n % lrows == 0;
-        const bool own = R > 1 && !dr && (!solo || rep); /* (directed: every target's row) */
-        lvl_hist_kernel<<<own ? 256 : 1024, 256, 0, st>>>(own ? (size_t)(rep ? lrows : nrows) * LVL_STRIDE : ncnt,
-                                                         own ? cnt + (size_t)row0 * LVL_STRIDE : cnt, dhist,
-                                                         rep ? (unsigned)(n / lrows) : 1u);
-        SRT_HIPCHK(hipGetLastError());
-        if (R > 1) {
-            SRT_HIPCHK(hipMemsetAsync(xbuf, 0, xn * sizeof(int32_t), st));
-            lvl_hist_limbs_kernel<<<1, LVL_STRIDE, 0, st>>>(1, dhist, xlimbs);
-            if (dr)
-                lvl_drank_counts_kernel<<<1, LVL_STRIDE, 0, st>>>(dhist, xcnt + (size_t)me * LVL_X_DCNT);
-            else
-                lvl_rank_counts_kernel<<<dim3(LVL_BATCH, solo ? R : 1), 256, 0, st>>>(n, ld, R, solo ? 0 : me, cnt, xcnt);
-            if (!directed && lrows > 0) { /* this rank's distinct light reliabilities, its block */
-                int32_t* hd = xblk + (size_t)me * LVL_GB * 2;
-                SRT_HIPCHK(hipMemsetAsync(H, 0xFF, LVL_RT_SLOTS * sizeof(unsigned long long), st));
-                /* the workgroup tables in the offsets' buffer (free until the offsets) */
-                size_t ntb = (ncnt + 1) * sizeof(int32_t) / (LVL_RT_LDS * sizeof(unsigned long long));
-                ntb = ntb < 512 ? ntb : 512;
-                ntb = ntb < (size_t)lrows ? ntb : (size_t)lrows;
-                const int nt = (int)(ntb > 0 ? ntb : 1);
-                unsigned long long* tabs = reinterpret_cast<unsigned long long*>(off);
-                lvl_rt_hash_stash_kernel<<<nt, 256, 0, st>>>(lrows, ld, LVL_BATCH, stash, scnt, r_rows, H,
-                                                             tabs, hd);
-                lvl_rt_merge_kernel<<<LVL_RT_LDS / 256 * srt_ceil_div(nt, LVL_RT_MC), 256, 0, st>>>(nt, tabs, H, hd);
-                lvl_rt_compact_kernel<<<1, 1024, 0, st>>>(H, map, reinterpret_cast<double*>(hd + 2), hd + 1);
-            }
-            SRT_HIPCHK(hipGetLastError());
-        }
-    }
     int rc;
-    unsigned long long* pin;
-    if ((rc = lvl_pinned(LVL_PIN_X + (R > 1 ? (xn + 1) / 2 + LVL_RT_CAP + 2 * LVL_BATCH + 4 : 4), &pin)))
-        return rc;
-    int32_t* hx = reinterpret_cast<int32_t*>(pin + LVL_PIN_X); /* the exchange, back on the host */
-    unsigned long long* ht = pin + LVL_PIN_X + (xn + 1) / 2;    /* the union table, then its flags */
-    int32_t* hwt = reinterpret_cast<int32_t*>(ht + LVL_RT_CAP + 2); /* the wire's per-weight base, block */
-    int32_t* hag = reinterpret_cast<int32_t*>(pin + LVL_PIN_AG);    /* the agreement, the failure flag */
-    int failed = !ok;
-    if (R > 1) {
-        hag[3] = failed;
-        SRT_HIPCHK(hipMemcpyAsync(xlimbs + 2 * LVL_STRIDE, &hag[3], sizeof(int32_t), hipMemcpyHostToDevice, st));
-        if ((rc = srt_coll_allreduce_i32(comm, xbuf, xn, 0, st))) return rc;
-        SRT_HIPCHK(hipMemcpyAsync(hx, xbuf, xn * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    }
-    unsigned long long hist[LVL_STRIDE];
-    if (R == 1)
-        SRT_HIPCHK(hipMemcpyAsync(pin + LVL_PIN_HIST, dhist, sizeof(hist), hipMemcpyDeviceToHost, st));
-    if ((rc = lvl_wait(st))) return rc;
-    if (R == 1) memcpy(hist, pin + LVL_PIN_HIST, sizeof(hist));
-    if (R > 1) { /* the summed histogram from its limbs, on the host (one read-back) */
-        failed = hx[2 * LVL_STRIDE];
-        for (int i = 0; i < LVL_STRIDE; i++)
-            hist[i] = (unsigned long long)(uint32_t)hx[i] + ((unsigned long long)(uint32_t)hx[LVL_STRIDE + i] << 20);
-    }
-    if (failed) return SRT_OK; /* out of device memory somewhere: Floyd-Warshall on every rank */
-    /* the union of every rank's distinct light reliabilities (sorted by bits: the same table on
-     * every rank) and, per weight <= LVL_BATCH, the largest rank's arcs (the streamed wire's
-     * block): both from the exchange, so the streamed extraction needs no further round trip */
-    /* The blocks come in hash-slot order and mostly repeat each other (C4: ~500 values per rank,
-     * the same ones), so they are deduplicated through an open-addressing set first and only the
-     * distinct values sorted: sorting the concatenation (4,000 values at N = 8) cost ~0.1-0.2 ms of
-     * host time on the critical path. A solo rank's peers hold its own values (their rows are
-     * shifted copies of its rows), so it pays the same. */
-    std::vector<unsigned long long> u;
-    bool fit = R > 1 && !dr; /* (the directed exchange carries no reliability blocks) */
-    if (fit) {
-        size_t all = 0;
-        for (int q = 0; q < R && fit; q++) {
-            const int32_t* hd = hx + LVL_X_LIMBS + (size_t)R * LVL_X_CNT + (size_t)(solo ? me : q) * LVL_GB * 2;
-            if (hd[0] || hd[1] > LVL_RT_CAP) fit = false;
-            all += (size_t)max(hd[1], 0);
-        }
-        size_t cap = 64;
-        while (cap < 2 * all) cap <<= 1;
-        std::vector<unsigned long long>& set = g_lvl_uset[srt_state_slot()];
-        set.assign(cap, ~0ull); /* (a NaN pattern: never a reliability's bits) */
-        int shift = 64;
-        for (size_t c = cap; c > 1; c >>= 1) --shift;
-        for (int q = 0; q < R && fit; q++) {
-            const int32_t* hd = hx + LVL_X_LIMBS + (size_t)R * LVL_X_CNT + (size_t)(solo ? me : q) * LVL_GB * 2;
-            const unsigned long long* v = reinterpret_cast<const unsigned long long*>(hd + 2);
-            for (int k = 0; k < hd[1]; ++k) {
-                size_t h = (size_t)((v[k] * 0x9E3779B97F4A7C15ull) >> shift);
-                while (set[h] != ~0ull && set[h] != v[k]) h = (h + 1) & (cap - 1);
-                if (set[h] == ~0ull) {
-                    set[h] = v[k];
-                    u.push_back(v[k]);
-                }
-            }
-        }
-        if (fit) {
-            std::sort(u.begin(), u.end());
-            fit = !u.empty() && u.size() <= (size_t)LVL_RT_CAP;
-        }
-    }
-    /* level budget from global quantities (the summed histogram, the largest shard's words): the
-     * largest L whose predicted time stays under half the FW time */
-    const double nw_all = (double)max_rows / 32.0;
-    int lmax = lvl_budget(hist, (double)n, nw_all, 0.5 * fw_ms);
-    /* and by memory: the planes (lmax x n x nw words) within half of what the device has left */
-    const size_t plane = (size_t)n * nw;
-    if (plane > 0) {
-        const size_t cap = lvl_avail_bytes() / 2 / (plane * sizeof(uint32_t));
-        if ((size_t)lmax > cap) lmax = (int)cap;
-    }
-    if (R > 1) { /* test hook: this rank's memory stands in for a smaller budget (lcap_r<rank>) */
-        char key[32];
-        snprintf(key, sizeof(key), "lcap_r%d", me);
-        const int lc = srt_form_int(key, -1);
-        if (lc >= 0 && lc < lmax) lmax = lc;
-    }
-    /* Every allocation of the build up front, softly, sized by THIS rank's budget: the agreed
-     * budget is the ranks' minimum, so the buffers fit it. Then one min all-reduce agrees the
-     * budget, the allocation outcome and whether the wire could be allocated. */
-    const int lmax_own = max(lmax, 0);
-    int64_t total64 = 0;
-    for (int x = 1; x <= lmax_own; ++x) total64 += (int64_t)hist[x];
-    const int32_t total_own = (int32_t)(total64 < 0x7FFFFFF0ll ? total64 : 0x7FFFFFF0ll);
-    uint32_t *arcs = NULL, *arcs2 = NULL, *aoff = NULL, *lev = NULL, *Rb = NULL;
-    double *ar = NULL, *ar2 = NULL;
-    int32_t* seg = NULL;
-    void *tmp = NULL, *stmp = NULL;
-    uint8_t* done = NULL;
-    size_t tmp_bytes = 0, sb = 0;
-    SRT_HIPCHK(hipcub::DeviceScan::ExclusiveSum(NULL, tmp_bytes, cnt, off, (int)(ncnt + 1), st));
-    const size_t dnt = (size_t)R * ((size_t)ld + 1) + 1; /* directed, N > 1: the runs' totals */
-    if (dr) {
-        size_t tb2 = 0;
-        SRT_HIPCHK(hipcub::DeviceScan::ExclusiveSum(NULL, tb2, cnt, off, (int)dnt, st));
-        tmp_bytes = max(tmp_bytes, tb2);
-    }
-    const bool need_sort_own = total_own > 0 && !(!directed && lmax_own <= LVL_STASH_W && hist[0] == 0);
-    if (need_sort_own)
-        SRT_HIPCHK(hipcub::DeviceSegmentedRadixSort::SortPairs(NULL, sb, arcs, arcs2, ar, ar2, total_own,
-                                                               ld, seg, seg + 1, 0, 24, st));
-    lvl_arena a2;
-    if (total64 <= 0x7FFFFFF0ll && lmax_own >= 2) {
-        a2.add(&tmp, tmp_bytes);
-        a2.add(&arcs, ((size_t)total_own + 8) * sizeof(uint32_t));
-        a2.add(&ar, ((size_t)total_own + 8) * sizeof(double));
-        if (need_sort_own) {
-            a2.add(&arcs2, ((size_t)total_own + 8) * sizeof(uint32_t));
-            a2.add(&ar2, ((size_t)total_own + 8) * sizeof(double));
-            a2.add(&seg, ((size_t)ld + 1) * sizeof(int32_t));
-            a2.add(&stmp, sb);
-        }
-        a2.add(&aoff, ((size_t)total_own + 64) * sizeof(uint32_t)); /* + a gather batch's tail */
-        a2.add(&lev, (size_t)lmax_own * plane * sizeof(uint32_t) + 16);
-        a2.add(&Rb, plane * sizeof(uint32_t) + 16);
-        a2.add(&done, (size_t)n * nchunk + 16);
-    }
-    /* the distinct arc reliabilities (packed post pass, n <= 32768) */
-    uint16_t* rix = NULL;
-    double* rtab = NULL;
-    if (total_own > 0 && n <= 32768) {
-        a2.add(&rix, ((size_t)total_own + 8) * sizeof(uint16_t));
-        a2.add(&rtab, LVL_RT_CAP * sizeof(double));
-    }
-    /* N > 1: the segments' reliability blocks (extract()), the counts' all-gather blocks (u16,
-     * every weight up to the budget), and the streamed wire's offsets at the shard starts */
-    double* gat = NULL;
-    if (total_own > 0 && n <= 32768 && R > 1 && !dr) a2.add(&gat, (size_t)R * LVL_GB * sizeof(double));
-    uint16_t* cg = NULL;
-    int32_t* packed = NULL;
-    if (R > 1 && !dr) {
-        a2.add(&cg, ((size_t)R * max_rows * max(lmax_own, 1) + 8) * sizeof(uint16_t));
-        a2.add(&packed, (size_t)4 * LVL_BATCH * 65 * sizeof(int32_t));
-    }
-    /* directed, N > 1: every rank's (target, weight <= budget) counts, the runs' totals and their
-     * scan, the fill's cursors, and the gathered blocks of arcs (12 B per arc, every rank's block
-     * padded to the largest; the ranks' arcs per weight are in the exchange) */
-    int32_t *tq = NULL, *oq = NULL, *dcur = NULL;
-    char* dwire = NULL;
-    auto dblock = [&](int lw) -> size_t { /* arcs of the largest rank's block, even */
-        uint64_t mx = 0;
-        for (int q = 0; q < R; q++) {
-            uint64_t t = 0;
-            for (int x = 1; x <= lw; ++x) {
-                const int32_t* c = hx + LVL_X_LIMBS + (size_t)q * LVL_X_DCNT + 2 * x;
-                t += (uint32_t)c[0] | ((uint32_t)c[1] << 16);
-            }
-            mx = t > mx ? t : mx;
-        }
-        return (size_t)((mx + 1) & ~(uint64_t)1);
-    };
-    if (dr) {
-        a2.add(&cg, ((size_t)R * ld * max(lmax_own, 1) + 8) * sizeof(uint16_t));
-        a2.add(&tq, dnt * sizeof(int32_t));
-        a2.add(&oq, dnt * sizeof(int32_t));
-        a2.add(&dcur, (ncnt + 1) * sizeof(int32_t));
-        a2.add(&dwire, (size_t)R * dblock(lmax_own) * 12 + 16);
-    }
-    commit(a2, &ok);
-    /* the streamed first extraction's wire (extract_streamed): every rank's block of a weight
-     * padded to the largest; needs the union table (fit) and at most 2 GB */
-    const int lx_own = min(lmax_own, LVL_BATCH);
-    size_t wire_words = 0;
-    for (int x = 1; x <= lx_own && R > 1; ++x) {
-        int mx = 0;
-        for (int q = 0; q < R; q++) {
-            const int32_t* c = hx + LVL_X_LIMBS + (size_t)q * LVL_X_CNT + (x - 1) * 2;
-            mx = max(mx, (int)((uint32_t)c[0] | ((uint32_t)c[1] << 16)));
-        }
-        wire_words += (size_t)R * mx;
-    }
-    int32_t* offw = NULL;
-    uint32_t* wire = NULL;
-    int stream_ok = R > 1 && !directed && hist[0] == 0 && fit && n <= 32768 && lx_own >= 1 &&
-                    srt_form_int("pkw", 1) != 0 && (double)wire_words * 4.0 < 2e9;
-    if (stream_ok && ok) {
-        int sok = 1;
-        lvl_arena a3;
-        a3.add(&offw, ((size_t)lx_own * ld + 1) * sizeof(int32_t));
-        /* (also the [weight][target] counts before their scan) */
-        a3.add(&wire, max(wire_words + 8, (size_t)lx_own * ld + 1) * sizeof(uint32_t));
-        commit(a3, &sok);
-        stream_ok = sok;
-    }
-    /* N > 1: what needs no agreed value is done on the side stream while the main stream
-     * carries the agreement and the count all-gather (on the main stream it delayed them): the
-     * level state's zeroing and, for the streamed extraction, the union table and the wire's
-     * per-weight bases, sized by this rank's budget (lx_own >= the agreed lx; the entries of the
-     * weights up to lx are the same either way). The main stream waits for it (wev[prep]) before
-     * the extraction; wasted when a rank falls back. */
-    hipEvent_t* wev = NULL; /* wev[w]: the arcs of weight w are in place on this rank */
-    hipStream_t wcs = NULL; /* the side stream */
-    const int prep = LVL_BATCH + 1;
-    bool prepped = false;
-    if (R > 1 && ok && Rb && done) { /* (not allocated under a budget below 2) */
-        if ((rc = lvl_side_stream(&wcs, &wev))) return rc;
-        SRT_HIPCHK(hipEventRecord(wev[prep], st)); /* the allocations are ordered on st */
-        SRT_HIPCHK(hipStreamWaitEvent(wcs, wev[prep], 0));
-        prepped = true;
-    }
-    if (R > 1) { /* the agreement goes out first; the side stream's calls are made under it */
-        hag[0] = lmax;
-        hag[1] = ok;
-        hag[2] = stream_ok;
-        SRT_HIPCHK(hipMemcpyAsync(dagree, hag, 3 * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        if ((rc = srt_coll_allreduce_i32(comm, dagree, 3, 1, st))) return rc;
-        SRT_HIPCHK(hipMemcpyAsync(hag, dagree, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    }
-    if (prepped) {
-        SRT_HIPCHK(hipMemsetAsync(Rb, 0, plane * sizeof(uint32_t), wcs));
-        SRT_HIPCHK(hipMemsetAsync(done, 0, (size_t)n * nchunk, wcs));
-        lvl_init_kernel<<<srt_ceil_div(nrows, 256), 256, 0, wcs>>>(n, row0, nrows, nw, Rb);
-        SRT_HIPCHK(hipGetLastError());
-    }
-    if (prepped && stream_ok && lev && rtab) {
-        SRT_HIPCHK(hipMemsetAsync(lev, 0, (size_t)lx_own * plane * sizeof(uint32_t), wcs));
-        const int nu = (int)u.size();
-        memcpy(ht, u.data(), u.size() * sizeof(unsigned long long));
-        const int hf[2] = {0, nu};
-        memcpy(ht + LVL_RT_CAP, hf, sizeof(hf));
-        SRT_HIPCHK(hipMemcpyAsync(rtab, ht, (size_t)nu * sizeof(double), hipMemcpyHostToDevice, wcs));
-        SRT_HIPCHK(hipMemcpyAsync(dflag, ht + LVL_RT_CAP, 2 * sizeof(int), hipMemcpyHostToDevice, wcs));
-        /* the wire: per weight every rank's block padded to the largest rank's arcs (from the
-         * exchange's per-rank counts): the weight's base and that block size */
-        size_t base = 0;
-        for (int w = 1; w <= lx_own; ++w) {
-            int mx = 0;
-            for (int q = 0; q < R; q++) {
-                const int32_t* c = hx + LVL_X_LIMBS + (size_t)q * LVL_X_CNT + (w - 1) * 2;
-                mx = max(mx, (int)((uint32_t)c[0] | ((uint32_t)c[1] << 16)));
-            }
-            hwt[2 * (w - 1)] = (int32_t)base;
-            hwt[2 * (w - 1) + 1] = mx;
-            base += (size_t)R * mx;
-        }
-        SRT_HIPCHK(hipMemcpyAsync(packed + LVL_BATCH * 65, hwt, 2 * (size_t)lx_own * sizeof(int32_t),
-                                  hipMemcpyHostToDevice, wcs));
-    }
-    if (prepped) SRT_HIPCHK(hipEventRecord(wev[prep], wcs));
-    if (R > 1) {
-        if ((rc = lvl_wait(st))) return rc;
-        lmax = hag[0];
-        ok = hag[1];
-        stream_ok = hag[2];
-    }
+    /* step 1: the counts and the exchange */
+    if ((rc = lvl_count_pass(b)) || (rc = lvl_exchange(b))) return rc;
+    if (b.failed) return SRT_OK; /* out of device memory somewhere: Floyd-Warshall on every rank */
+    /* this rank's plan: the union table, the budget, every buffer; step 2 agrees it */
+    b.fit = R > 1 && !b.dr && /* (the directed exchange carries no reliability blocks) */
+            lvl_union(reinterpret_cast<const unsigned long long*>(b.hx + LVL_X_LIMBS + (size_t)R * LVL_X_CNT), R,
+                      b.solo ? b.me : -1, *b.u);
+    b.lmax = lvl_own_budget(b);
+    if ((rc = lvl_alloc_all(b)) || (rc = lvl_agree(b))) return rc;
     /* From here every branch reads agreed or global values only: hist is summed over the ranks
      * (hist[0] is the stash-overflow count), the budget, the allocation outcome and the wire are
      * agreed. In-arcs come out of the ordered stash already in (weight, source) order, on every
      * rank, when no row overflowed its stash: no sort. */
     int wmin = 0;
     for (int x = 1; x <= LVL_WMAX && !wmin; ++x)
-        if (hist[x]) wmin = x;
-    if (lmax < 2 || !wmin || wmin > lmax) return SRT_OK;
-    total64 = 0;
-    for (int x = 1; x <= lmax; ++x) total64 += (int64_t)hist[x];
+        if (b.hist[x]) wmin = x;
+    if (b.lmax < 2 || !wmin || wmin > b.lmax) return SRT_OK;
+    const int64_t total64 = lvl_arcs_upto(b.hist, b.lmax);
     if (total64 > 0x7FFFFFF0ll) return SRT_OK; /* int32 arc offsets (global) */
-    if (!ok) return SRT_OK; /* out of device memory somewhere: Floyd-Warshall on every rank */
-    const int32_t total = (int32_t)total64;
-    const bool want_rt = total > 0 && n <= 32768;
+    if (!b.ok) return SRT_OK; /* out of device memory somewhere: Floyd-Warshall on every rank */
+    b.want_rt = total64 > 0 && n <= 32768;
     /* The in-arcs are extracted for the first batch of levels only (w <= lx = min(lmax, LVL_BATCH):
      * levels d <= lx use no heavier arc) and again up to lmax if the levels run past it: C4 ends
      * at level 5, and its ~20-quantum budget would extract, number and (N > 1) send 2.5x the arcs
      * it uses. The counts stay whole (narrow offsets) for the second extraction. */
-    const int lx = min(lmax, LVL_BATCH);
-    /* every target's counts of weights w0..w1 on every rank (a solo rank has them: synthesised) */
-    lvl_dcnt dcn{NULL, NULL, 0, 0, ld}; /* directed, N > 1: the gathered per-rank counts */
-    auto share_counts = [&](int w0, int w1) -> int {
-        if (R == 1 || w1 < w0) return SRT_OK;
-        if (dr) { /* every rank's contribution to every target: summed, and kept per rank (dcnt) */
-            const size_t dblk = (size_t)ld * (w1 - w0 + 1);
-            uint16_t* reg = cg + (size_t)R * ld * (w0 - 1); /* weights 1..lx, then lx + 1..lmax */
-            lvl_dcnt_pack_kernel<<<srt_ceil_div(ld, 256), 256, 0, st>>>(ld, w0, w1, cnt, reg + (size_t)me * dblk);
-            SRT_HIPCHK(hipGetLastError());
-            int rc_ = srt_coll_allgather(comm, reg, dblk * sizeof(uint16_t), st);
-            if (rc_) return rc_;
-            lvl_dcnt_sum_kernel<<<srt_ceil_div(ld, 256), 256, 0, st>>>(ld, R, w0, w1, reg, cnt);
-            SRT_HIPCHK(hipGetLastError());
-            if (w0 == 1) dcn = lvl_dcnt{reg, NULL, w1, w1, ld};
-            else dcn.b = reg, dcn.wb = w1;
-            return SRT_OK;
-        }
-        const size_t blk = (size_t)max_rows * (w1 - w0 + 1);
-        if (nrows > 0)
-            lvl_cnt_gpack_kernel<<<srt_ceil_div(nrows, 256), 256, 0, st>>>(row0, nrows, max_rows, w0, w1, me,
-                                                                           cnt, cg);
-        SRT_HIPCHK(hipGetLastError());
-        int rc_ = srt_coll_allgather(comm, cg, blk * sizeof(uint16_t), st);
-        if (rc_) return rc_;
-        if (!solo) lvl_cnt_gunpack_kernel<<<srt_ceil_div(ld, 256), 256, 0, st>>>(ld, R, max_rows, w0, w1, cg, cnt);
-        SRT_HIPCHK(hipGetLastError());
-        return SRT_OK;
-    };
-    if ((rc = share_counts(1, lx))) return rc; /* the first extraction's weights */
-    /* offsets of the (target, weight <= lw) in-arcs: narrow scan, counts untouched */
-    auto offsets = [&](int lw, int32_t* ow = NULL, int32_t* osz = NULL) -> int {
-        if (lw <= LVL_BATCH) { /* a first extraction: two launches (with the wire's offsets) */
-            const int nb = (ld + 1 + 255) / 256; /* (the thread of target ld writes the totals) */
-            lvl_off_part_kernel<<<nb, 256, 0, st>>>(ld, lw, cnt, tb);
-            lvl_offsets_kernel<<<nb, 256, 0, st>>>(ld, lw, R, cnt, tb, off, ow, osz);
-            SRT_HIPCHK(hipGetLastError());
-            return SRT_OK;
-        }
-        lvl_tot_kernel<<<srt_ceil_div(ld + 1, 256), 256, 0, st>>>(ld, lw, cnt, tb);
-        SRT_HIPCHK(hipGetLastError());
-        SRT_HIPCHK(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, tb, tb + ld + 1, ld + 1, st));
-        lvl_off_kernel<<<srt_ceil_div(ld + 1, 256), 256, 0, st>>>(ld, lw, cnt, tb + ld + 1, off);
-        SRT_HIPCHK(hipGetLastError());
-        return SRT_OK;
-    };
-    uint32_t* const arcsA = arcs;
-    double* const arA = ar;
-    int32_t total_x = 0;          /* the arcs of the current extraction */
-    auto extract = [&](int lw) -> int {
-        int numbered = 0; /* the segments travelled as arcs + table indices */
-        int64_t t64 = 0;
-        for (int x = 1; x <= lw; ++x) t64 += (int64_t)hist[x];
-        total_x = (int32_t)t64;
-        const int sorted_w = !directed && lw <= LVL_STASH_W && hist[0] == 0; /* global values */
-        int rc_ = offsets(lw); /* (target, weight <= lw)-major */
-        if (rc_) return rc_;
-        if (dr) { /* this rank's arcs into its block, the blocks all-gathered once, then placed */
-            const size_t blk = dblock(lw) * 12; /* (from the exchange: alike on every rank) */
-            lvl_dtot_kernel<<<(unsigned)((dnt + 255) / 256), 256, 0, st>>>(R, lw, dcn, tq);
-            SRT_HIPCHK(hipGetLastError());
-            SRT_HIPCHK(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, tq, oq, (int)dnt, st));
-            lvl_dcur_kernel<<<srt_ceil_div(ld, 256), 256, 0, st>>>(me, lw, dcn, oq, dcur);
-            char* mine = dwire + (size_t)me * blk;
-            if (lrows > 0)
-                lvl_arcs_colwin_kernel<true><<<dim3(ld / 64, srt_ceil_div(lrows, LVL_DROWS)), 256, 0, st>>>(
-                    n, ld, row0, lrows, w_rows, dcur, lw, reinterpret_cast<uint32_t*>(mine), r_rows,
-                    reinterpret_cast<double*>(mine + blk / 3));
-            SRT_HIPCHK(hipGetLastError());
-            if ((rc_ = srt_coll_allgather(comm, dwire, blk, st))) return rc_;
-            lvl_dplace_kernel<<<srt_ceil_div(n, 4), 256, 0, st>>>(n, ld, R, blk, off, tq, oq, dwire, arcsA, arA);
-        } else if (directed)
-            lvl_arcs_cols_kernel<true><<<ld / 64, 256, 0, st>>>(n, ld, w_rows, NULL, lw, off, arcsA,
-                                                                r_rows, arA);
-        else
-            lvl_arcs_rows_kernel<true><<<nrows, 256, 0, st>>>(n, ld, row0, w_rows, NULL, lw, off, arcsA,
-                                                              r_rows, arA, NULL, stash, scnt);
-        SRT_HIPCHK(hipGetLastError());
-        if (R > 1 && !dr) { /* every rank filled its rows' segment: broadcast the segments */
-            int32_t hoff[65];
-            for (int q = 0; q <= R; q++) {
-                int32_t b = ld, e = ld;
-                if (q < R) srt_shard_rows(ld, SRT_SHARD_ALIGN, R, q, &b, &e);
-                SRT_HIPCHK(hipMemcpyAsync(&hoff[q], off + (size_t)b * LVL_STRIDE, sizeof(int32_t),
-                                          hipMemcpyDeviceToHost, st));
-            }
-            if ((rc_ = lvl_wait(st))) return rc_;
-            /* Numbered segments: the packed post pass needs each arc's index into the table of
-             * distinct reliabilities, not its f64. Each rank numbers its own segment's values
-             * (hash + compact), the blocks are all-gathered (16 KB per rank), every rank takes
-             * the union sorted by value bits -- the same table everywhere -- and the segments
-             * travel as arcs + u16 indices: 6 B per arc instead of 12. Taken when the post pass
-             * will be the packed one (levels <= lw <= 31, pkw) and the fill needs no sort (the
-             * sort carries the f64s); more than LVL_RT_CAP values in the union (or a probe
-             * overflow) keeps the f64 segments, on every rank alike. */
-            const int me = srt_comm_rank(comm);
-            /* the arcs this process numbers: its own segment, or (solo) every segment at once,
-             * in block 0 */
-            const int nb0 = hoff[me], nb1 = hoff[me + 1], qb = me;
-            if (gat && sorted_w && lw <= 31 && srt_form_int("pkw", 1) != 0) {
-                SRT_HIPCHK(hipMemsetAsync(gat, 0, (size_t)R * LVL_GB * sizeof(double), st));
-                if (nb1 > nb0) {
-                    SRT_HIPCHK(hipMemsetAsync(dflag, 0, 2 * sizeof(int), st));
-                    SRT_HIPCHK(hipMemsetAsync(H, 0xFF, LVL_RT_SLOTS * sizeof(unsigned long long), st));
-                    lvl_rt_hash_kernel<<<lvl_rt_grid(nb1 - nb0), 256, 0, st>>>(NULL, NULL, nb0, nb1, arA, H,
-                                                                              rix, dflag);
-                    lvl_rt_compact_kernel<<<1, 1024, 0, st>>>(H, map, gat + qb * LVL_GB + 1, dflag + 1);
-                    SRT_HIPCHK(hipGetLastError());
-                    SRT_HIPCHK(hipMemcpyAsync(gat + qb * LVL_GB, dflag, 2 * sizeof(int),
-                                              hipMemcpyDeviceToDevice, st));
-                }
-                if ((rc_ = srt_coll_allgather(comm, gat, LVL_GB * sizeof(double), st))) return rc_;
-                std::vector<unsigned long long> hg((size_t)R * LVL_GB);
-                SRT_HIPCHK(hipMemcpyAsync(hg.data(), gat, hg.size() * sizeof(unsigned long long),
-                                          hipMemcpyDeviceToHost, st));
-                if ((rc_ = lvl_wait(st))) return rc_;
-                std::vector<unsigned long long> u;
-                bool fit = true;
-                for (int q = 0; q < R && fit; q++) {
-                    int hd[2];
-                    memcpy(hd, &hg[(size_t)q * LVL_GB], sizeof(hd));
-                    if (hd[0] || hd[1] > LVL_RT_CAP) fit = false;
-                    else u.insert(u.end(), hg.begin() + (size_t)q * LVL_GB + 1,
-                                  hg.begin() + (size_t)q * LVL_GB + 1 + hd[1]);
-                }
-                if (fit) {
-                    std::sort(u.begin(), u.end());
-                    u.erase(std::unique(u.begin(), u.end()), u.end());
-                    fit = !u.empty() && u.size() <= (size_t)LVL_RT_CAP;
-                }
-                if (fit) {
-                    const int nu = (int)u.size(), hf[2] = {0, nu};
-                    SRT_HIPCHK(hipMemcpyAsync(rtab, u.data(), u.size() * sizeof(double),
-                                              hipMemcpyHostToDevice, st));
-                    SRT_HIPCHK(hipMemcpyAsync(dflag, hf, sizeof(hf), hipMemcpyHostToDevice, st));
-                    if (nb1 > nb0)
-                        lvl_rt_index_kernel<<<srt_ceil_div(nb1 - nb0, 256), 256, 0, st>>>(
-                            nb1 - nb0, arA + nb0, reinterpret_cast<const unsigned long long*>(rtab), nu,
-                            rix + nb0);
-                    SRT_HIPCHK(hipGetLastError());
-                    if ((rc_ = lvl_wait(st))) return rc_; /* hf and u leave scope */
-                    numbered = 1;
-                }
-            }
-            rc_ = srt_coll_group_begin(comm);
-            for (int q = 0; q < R && !rc_; q++)
-                if (hoff[q + 1] > hoff[q]) {
-                    const size_t c = (size_t)(hoff[q + 1] - hoff[q]);
-                    rc_ = srt_coll_bcast(comm, arcsA + hoff[q], c * sizeof(uint32_t), q, st);
-                    if (!rc_)
-                        rc_ = numbered ? srt_coll_bcast(comm, rix + hoff[q], c * sizeof(uint16_t), q, st)
-                                       : srt_coll_bcast(comm, arA + hoff[q], c * sizeof(double), q, st);
-                }
-            const int rc2 = srt_coll_group_end(comm);
-            if (rc_ || rc2) return rc_ ? rc_ : rc2;
-            if (solo && lrows > 0) {
-                lvl_solo_arcs_kernel<<<srt_ceil_div(n, 4), 256, 0, st>>>(n, row0, nrows, lrows, 1, lw, nw, off,
-                                                                         arcsA, numbered ? rix : NULL,
-                                                                         numbered ? NULL : arA, NULL);
-                SRT_HIPCHK(hipGetLastError());
-            }
-        }
-        /* in-arcs of each target sorted by (weight, source vertex): the order the predecessor
-         * search walks them in (the full-row fill's atomics leave the order inside a weight
-         * arbitrary; the ordered stash fill needs no sort) */
-        arcs = arcsA;
-        ar = arA;
-        if (total_x > 0 && !sorted_w) {
-            lvl_segs_kernel<<<srt_ceil_div(ld + 1, 256), 256, 0, st>>>(ld, off, seg);
-            SRT_HIPCHK(hipGetLastError());
-            SRT_HIPCHK(hipcub::DeviceSegmentedRadixSort::SortPairs(stmp, sb, arcsA, arcs2, arA, ar2,
-                                                                   total_x, ld, seg, seg + 1, 0, 24,
-                                                                   st));
-            arcs = arcs2;
-            ar = ar2;
-        }
-        if (total_x > 0) {
-            lvl_aoff_kernel<<<srt_ceil_div(total_x, 256), 256, 0, st>>>(total_x, nw, arcs, aoff);
-            SRT_HIPCHK(hipGetLastError());
-        }
-        /* the reliability table: its flags are read with the levels' completion (no round trip) */
-        if (want_rt && total_x > 0 && !numbered) {
-            SRT_HIPCHK(hipMemsetAsync(dflag, 0, 2 * sizeof(int), st));
-            SRT_HIPCHK(hipMemsetAsync(H, 0xFF, LVL_RT_SLOTS * sizeof(unsigned long long), st));
-            lvl_rt_hash_kernel<<<lvl_rt_grid(total_x), 256, 0, st>>>(NULL, NULL, 0, total_x, ar, H, rix, dflag);
-            lvl_rt_compact_kernel<<<1, 1024, 0, st>>>(H, map, rtab, dflag + 1);
-            lvl_rt_remap_kernel<<<srt_ceil_div(total_x, 256), 256, 0, st>>>(total_x, map, rix);
-            SRT_HIPCHK(hipGetLastError());
-        }
-        return 0;
-    };
-    int streamed = 0;       /* the weights the streamed extraction delivers on the side stream */
-    int wnum = 0;           /* its arcs carry table indices (else their f64s travel beside) */
-    /* N > 1, the first extraction: the arcs of weight <= lw streamed weight by weight on the side
-     * stream (the kernels above); level d then waits for ev[d - 1] only. Taken when the fill is the
-     * ordered stash (sorted_w) and the reliabilities can be numbered; otherwise extract(). One
-     * host round trip: the gathered reliability blocks and the wire offsets come back together. */
-    auto extract_streamed = [&](int lw) -> int {
-        int64_t t64 = 0;
-        for (int x = 1; x <= lw; ++x) t64 += (int64_t)hist[x];
-        total_x = (int32_t)t64;
-        int rc_;
-        /* offsets over the arcs with w <= lw, (target, weight)-major, and the wire's: offw, the
-         * [weight][target] scan of every target's counts (gathered), dsz its values at the shard
-         * starts; the wire's per-weight bases are on the device since the agreement */
-        int32_t* const dsz = packed;
-        const int32_t* dwt = packed + LVL_BATCH * 65;
-        if ((rc_ = offsets(lw, offw, dsz))) return rc_;
-        lvl_arcs_rows_kernel<true><<<nrows, 256, 0, st>>>(n, ld, row0, w_rows, NULL, lw, off, arcsA,
-                                                          r_rows, arA, NULL, stash, scnt);
-        const int32_t* lo = off + (size_t)row0 * LVL_STRIDE;
-        const int32_t* hi = off + (size_t)(row0 + nrows) * LVL_STRIDE;
-        /* each own arc's row offset and its index into the union table (on the device since the
-         * agreement) */
-        lvl_own_index_kernel<<<512, 256, 0, st>>>(lo, hi, nw, arcsA, arA,
-                                                  reinterpret_cast<const unsigned long long*>(rtab), (int)u.size(),
-                                                  aoff, rix);
-        if (lrows > 0)
-            lvl_wire_pack_kernel<<<srt_ceil_div(lrows, 4), 256, 0, st>>>(ld, row0, lrows, lw, R, me, off, offw, dsz,
-                                                                        dwt, arcsA, rix, arA, wire, NULL);
-        SRT_HIPCHK(hipGetLastError());
-        SRT_HIPCHK(hipEventRecord(wev[0], st));
-        SRT_HIPCHK(hipStreamWaitEvent(wcs, wev[0], 0));
-        /* while weight 1 travels: the own sources' arcs into their planes (zeroed since the
-         * agreement) */
-        if (solo && lrows > 0)
-            lvl_solo_direct_kernel<<<srt_ceil_div(n, 4), 256, 0, st>>>(n, row0, nrows, lrows, nw, lw, plane, off,
-                                                                       arcsA, lev, Rb);
-        else if (!solo && lrows > 0)
-            lvl_direct_kernel<<<srt_ceil_div(lrows, 4), 256, 0, st>>>(row0, row0 + lrows, nw, lw, plane, off,
-                                                                     arcsA, lev, Rb);
-        SRT_HIPCHK(hipGetLastError());
-        wnum = 1;
-        arcs = arcsA;
-        ar = arA;
-        streamed = lw;
-        return 0;
-    };
-    /* weight w of the streamed extraction on the side stream: the all-gather of the blocks, their
-     * placement (the solo rank synthesises its peers' arcs instead), and, after the last weight of
-     * a build whose reliabilities were not numbered, the local table over every arc. Enqueued just
-     * before level w, so the host's calls for weight w + 1 overlap the levels on the GPU. */
-    auto stream_weight = [&](int w) -> int {
-        const size_t base = (size_t)hwt[2 * (w - 1)], mx = (size_t)hwt[2 * (w - 1) + 1];
-        int rc_ = srt_coll_allgather(comm, wire + base, mx * sizeof(uint32_t), wcs);
-        if (rc_) return rc_;
-        SRT_HIPCHK(hipEventRecord(wev[w], wcs));
-        return SRT_OK;
-    };
-    /* Weight w's placement, on the main stream between two levels: the all-gather finished under
-     * the previous level, and the whole GPU places the arcs in ~12 us. On the side stream the
-     * placement got only the CUs the persistent level grid left free and ended with the level
-     * it ran beside (72-135 us per weight on one rank of N = 8), and the last weight's all-gather
-     * queued behind it. */
-    int wp = 0; /* the streamed weights placed so far */
-    auto place_weight = [&](int w) -> int {
-        const int32_t* dsz = packed;
-        const int32_t* dwt = packed + LVL_BATCH * 65;
-        SRT_HIPCHK(hipStreamWaitEvent(st, wev[w], 0));
-        if (solo && lrows > 0)
-            lvl_solo_arcs_kernel<<<srt_ceil_div(n, 4), 256, 0, st>>>(n, row0, nrows, lrows, w, w, nw, off, arcs,
-                                                                     wnum ? rix : NULL, wnum ? NULL : ar, aoff);
-        else if (!solo)
-            lvl_wire_unpack_kernel<<<srt_ceil_div(n, 4), 256, 0, st>>>(n, ld, row0, nrows, w, nw, R, off, offw,
-                                                                       dsz, dwt, wire, NULL, arcs, rix, ar, aoff);
-        SRT_HIPCHK(hipGetLastError());
-        return SRT_OK;
-    };
-    if (R == 1) {
-        SRT_HIPCHK(hipMemsetAsync(Rb, 0, plane * sizeof(uint32_t), st));
-        SRT_HIPCHK(hipMemsetAsync(done, 0, (size_t)n * nchunk, st));
-        lvl_init_kernel<<<srt_ceil_div(nrows, 256), 256, 0, st>>>(n, row0, nrows, nw, Rb);
+    b.lx = min(b.lmax, LVL_BATCH);
+    if ((rc = lvl_share_counts(b, 1, b.lx))) return rc; /* step 3: the first extraction's weights */
+    if (R == 1) { /* (N > 1: zeroed on the side stream since the agreement) */
+        SRT_HIPCHK(hipMemsetAsync(b.Rb, 0, b.plane * sizeof(uint32_t), st));
+        SRT_HIPCHK(hipMemsetAsync(b.done, 0, (size_t)n * b.nchunk, st));
+        lvl_init_kernel<<<srt_ceil_div(nrows, 256), 256, 0, st>>>(n, row0, nrows, b.nw, b.Rb);
         SRT_HIPCHK(hipGetLastError());
     }
-    if (prepped) SRT_HIPCHK(hipStreamWaitEvent(st, wev[prep], 0));
-    if ((rc = stream_ok ? extract_streamed(lx) : extract(lx))) return rc;
-    unsigned nblk = (unsigned)(((n + 3) / 4) * nchunk);
-    nblk = (nblk + 7u) & ~7u;
-    /* while the streamed arcs are still arriving, one CU per XCD stays free for the broadcast
-     * (RCCL's kernels, the unpack) beside the persistent level grid */
-    const unsigned pgrid = lvl_grid((const void*)lvl_step_kernel, nblk, streamed ? 8 : 0);
-    /* the levels in batches of LVL_BATCH, one host round trip per batch. After the first batch
-     * the settled fraction decides whether the rest is worth it: a graph with far-apart vertices
-     * (metric latencies, C4metric: 0.2% settled after 8 levels, distances of hundreds of quanta)
-     * goes to the FW at once instead of spending its whole budget first (77 ms there). At N > 1
-     * the decision is taken from the summed vote (lvl_vote_kernel): the fraction of all n^2 pairs,
-     * the same number on every rank and the one a single GPU would see. A rank whose own sources
-     * settled early runs the later levels as no-ops (lvl_step_kernel's prev test) and keeps its D. */
-    int D = 0, all_done = 0, hflag[2] = {0, 0};
-    unsigned long long* nset = reinterpret_cast<unsigned long long*>(dagree + 4);
-    unsigned long long* ngath = nset + 1; /* the level kernels' gathered bytes (dhist word 515) */
-    const int ev0 = evp ? evp->used : 0;
-    if (evp && (rc = evpool_reserve(evp, ev0 + 2 * lmax))) return rc;
-    int wq = 0; /* the streamed weights enqueued so far */
-    for (int d0 = 1, d1 = 0; d0 <= lmax; d0 = d1 + 1) {
-        /* batches: levels 1-5 (C4's distances end at 4-5), then one level at a time up to
-         * LVL_BATCH (a level nobody needs is never launched, nor its weight waited for), then
-         * LVL_BATCH at a time */
-        d1 = d0 == 1 ? min(lmax, LVL_B1) : d0 <= LVL_BATCH ? d0 : min(lmax, d0 + LVL_BATCH - 1);
-        for (int d = d0; d <= d1; ++d) {
-            /* weights go out one ahead of the levels (every rank alike: a settled rank still sends
-             * its arcs), but not past the batch they are for: a weight nobody's level needs is
-             * never sent (C4 ends at level 5) */
-            while (wq < min(streamed, min(d + 1, d1)))
-                if ((rc = stream_weight(++wq))) return rc;
-            if (D && d > D) continue; /* this rank's sources are settled: nothing to run */
-            /* Level d reads the arcs of weight < d only: an arc of weight d counts for its own
-             * source alone (Delta_0), and lvl_direct_kernel put those into the planes from this
-             * rank's rows. So level d waits for weight d - 1, and level 1 for nothing. */
-            while (wp < min(d - 1, wq))
-                if ((rc = place_weight(++wp))) return rc;
-            if (evp) SRT_HIPCHK(hipEventRecord(evp->ev[evp->used++], st));
-            if (d == 1) { /* the weight-1 arcs as bits; level 2 takes up the completion flags
-                           * (dinc[1] stays set: a graph settled at level 1 reports 2 levels).
-                           * Streamed: lvl_direct_kernel has set them. */
-                SRT_HIPCHK(hipMemsetAsync(dinc + 1, 0xFF, sizeof(int), st));
-                if (!streamed) {
-                    SRT_HIPCHK(hipMemsetAsync(lev, 0, plane * sizeof(uint32_t), st));
-                    lvl_first_kernel<<<srt_ceil_div(n, 4), 256, 0, st>>>(n, nw, row0, nrows, off, arcs,
-                                                                          lev, Rb);
-                }
-            } else {
-                /* levels 2 and 3: the weight-d and weight-(d - 1) groups from the in-arc runs
-                 * (lvl_near_kernel); later levels stop after their first group almost
-                 * everywhere (the early exit), so they keep the gathers. The runs are read whole
-                 * for every target whatever a rank's share of the sources, so they pay only for
-                 * a wide share (C4: 14.5 -> 14.1 ms on one GPU; a rank of N = 8, 128 words,
-                 * went 2.55 -> 2.86 ms) */
-                const bool near = d <= 3 && d <= lx && nw >= LVL_NEAR_MIN_NW && nw <= LVL_NEAR_NW;
-                if (near)
-                    lvl_near_kernel<<<srt_ceil_div(n, 4), 256, 4 * (size_t)nw * sizeof(uint32_t), st>>>(
-                        d, n, nw, row0, nrows, d <= streamed, off, arcs, lev);
-                lvl_step_kernel<<<pgrid, 256, 0, st>>>(d, near ? 2 : d <= streamed, n, nw, nchunk, row0, nrows, nblk,
-                                                      off, arcs, aoff, lev, Rb, done, dinc + d,
-                                                      dinc + d - 1, nset, ngath);
-            }
-            if (evp) SRT_HIPCHK(hipEventRecord(evp->ev[evp->used++], st));
-        }
-        SRT_HIPCHK(hipGetLastError());
-        /* the batch's weights in place before anything after its levels (the post pass reads
-         * every arc up to the last level) */
-        while (wp < wq)
-            if ((rc = place_weight(++wp))) return rc;
-        if (R > 1) {
-            lvl_vote_kernel<<<1, 64, 0, st>>>(dinc + d1, nset, dvote);
-            SRT_HIPCHK(hipGetLastError());
-            if ((rc = srt_coll_allreduce_i32(comm, dvote, 4, 0, st))) return rc;
-        }
-        /* one read-back: the completion flags, the table flags, the settled pairs and the vote
-         * are neighbours in the host-side words (four copies cost ~20 us each of round trip) */
-        unsigned long long* const hw = pin + LVL_PIN_HW;
-        SRT_HIPCHK(hipMemcpyAsync(hw, dhist + LVL_H_INC, (LVL_H_WORDS - LVL_H_INC) * sizeof(unsigned long long),
-                                  hipMemcpyDeviceToHost, st));
-        if ((rc = lvl_wait(st))) return rc;
-        const int* hinc = reinterpret_cast<const int*>(hw);
-        const int32_t* vote = reinterpret_cast<const int32_t*>(hw + (LVL_H_VOTE - LVL_H_INC));
-        unsigned long long settled = hw[LVL_H_AGREE + 2 - LVL_H_INC];
-        hflag[0] = hinc[LVL_WMAX + 1];
-        hflag[1] = hinc[LVL_WMAX + 2];
-        int inc[LVL_BATCH];
-        for (int d = d0; d <= d1; ++d) inc[d - d0] = hinc[d];
-        for (int d = d0; d <= d1 && !D; ++d)
-            if (inc[d - d0] == 0) D = d;
-        if (R > 1) {
-            all_done = vote[0] == 0;
-            settled = (unsigned long long)(uint32_t)vote[1] + ((unsigned long long)(uint32_t)vote[2] << 21) +
-                      ((unsigned long long)(uint32_t)vote[3] << 42);
-        } else {
-            all_done = D != 0;
-        }
-        if (all_done) break;
-        /* settled pairs of all sources: the levels >= 2 counted by lvl_step_kernel, every source's
-         * own vertex (level 0) and the weight-1 arcs (level 1, lvl_first_kernel counts none) */
-        const double frac = ((double)settled + (double)n + (double)hist[1]) / ((double)n * (double)n);
-        /* at the end of the first LVL_BATCH levels (a forced level build, fw_ms = 1e30 from
-         * SRT_FORM levels=1, runs its whole budget) */
-        if (d1 == lx && d1 < lmax && frac < LVL_MIN_SETTLED && fw_ms < 1e29)
-            break; /* -> Floyd-Warshall, every rank */
-        if (d1 == lx && lx < lmax) { /* the heavier arcs: their counts, then every arc up to lmax */
-            while (wq < streamed) /* (the first extraction's last weights, for the collectives) */
-                if ((rc = stream_weight(++wq))) return rc;
-            while (wp < wq) /* its writes come first */
-                if ((rc = place_weight(++wp))) return rc;
-            if ((rc = share_counts(lx + 1, lmax)) || (rc = extract(lmax))) return rc;
-        }
-    }
-    /* the side stream's last weight before anything frees the wire (lvl_free waits for it too) */
-    if (wq) L->wlast = wev[wq];
-    if (evp && D) evp->used = ev0 + 2 * D; /* the levels that did work */
-    /* the bytes the level kernels gathered, counted on the device (the early exit skips the
-     * later weight groups of a unit, so the model -- every arc of weight < d for every level --
-     * would overstate them) */
-    const unsigned long long* hw_last = pin + LVL_PIN_HW; /* the last batch's read-back */
-    const int64_t gathered = (int64_t)hw_last[LVL_H_AGREE + 3 - LVL_H_INC];
-    if (!all_done) return SRT_OK; /* the verdict, alike on every rank (the summed vote) */
-    int ntab = 0;
-    if (want_rt && !hflag[0] && hflag[1] <= LVL_RT_CAP)
-        ntab = hflag[1];
-    else
-        rix = NULL, rtab = NULL; /* (freed with the state) */
-    /* the packed post pass writes the u32 rows itself (rel_pk_kernel): the table of distinct arc
-     * reliabilities, 5-bit levels and u16 vertices (n <= 32768) */
-    /* 1: the packed words with the level, source-major from lvl_pred_rows_kernel (with the tie
-     * count: as 2), then rel_pk_kernel, which writes the u32 rows too (SRT_FORM pkw=3, 4: the
-     * same with srt_levels_pred's units forced to one sub-chunk, to whole chunks); 2 (SRT_FORM pkw=2):
-     * lvl_pred_kernel's target-major words and one transpose before rel_pk_kernel; 0 (past the
-     * packed form, or SRT_FORM pkw=0): lvl_out8 rows + the predecessor rows + rel_tree_kernel */
-    const int fpkw = srt_form_int("pkw", 1);
-    const int pkw = rix && D <= 31 && n <= 32768 ? (fpkw == 2 ? 2 : fpkw != 0) : 0;
-    uint8_t* l8 = NULL;
-    uint32_t* apk = NULL;
-    if (pkw == 1 && total_x > 0) { /* 4 B per held arc (34 MB on C4), freed with the state */
-        LVL_ALLOC(apk, (size_t)total_x * sizeof(uint32_t));
-        lvl_apk_kernel<<<srt_ceil_div(total_x, 256), 256, 0, st>>>(total_x, arcs, rix, apk);
-        SRT_HIPCHK(hipGetLastError());
-    }
-    if (!pkw) {
-        LVL_ALLOC(l8, (size_t)nrows * ld);
-        if (D <= LVL_OUT_L) {
-            const int lds = D * 2 * 256 * (int)sizeof(uint4);
-            SRT_HIPCHK(hipFuncSetAttribute((const void*)lvl_out8_kernel,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            lvl_out8_kernel<<<dim3(srt_ceil_div(ld, 256), srt_ceil_div(nw, 8)), 256, lds, st>>>(
-                n, ld, nw, row0, D, lev, lat_rows, l8);
-        } else {
-            lvl_out_kernel<<<dim3(srt_ceil_div(ld, 1024), srt_ceil_div(nw, 16)), 256, 0, st>>>(
-                n, ld, nw, row0, D, lev, lat_rows, l8);
-        }
-        SRT_HIPCHK(hipGetLastError());
-    }
-    *levels = D;
-    *gather_bytes = gathered;
-    L->held = 1;
-    L->n = n;
-    L->nw = nw;
-    L->nchunk = nchunk;
-    L->row0 = row0;
-    L->nrows = nrows;
-    L->D = D;
-    L->nblk = nblk;
-    L->off = off;
-    L->arcs = arcs;
-    L->aoff = aoff;
-    L->ar = ar;
-    L->rix = rix;
-    L->apk = apk;
-    L->rtab = rtab;
-    L->ntab = ntab;
-    L->lev = lev;
-    L->l8 = l8;
-    L->pkw = pkw;
-    L->total = total_x;
-    L->pn_cap = lvl_pn_cap(hist, n, nrows, D);
-    L->dkey = dkey; /* the diagonal keys of this rank's rows */
-    L->r_rows = r_rows;
-    return SRT_OK;
+    if (b.prepped) SRT_HIPCHK(hipStreamWaitEvent(st, b.wev[LVL_PREP], 0));
+    /* step 4, then step 5 */
+    if ((rc = b.stream_ok ? lvl_extract_streamed(b, b.lx) : lvl_extract(b, b.lx))) return rc;
+    if ((rc = lvl_levels(b))) return rc;
+    if (!b.all_done) return SRT_OK; /* the verdict, alike on every rank (the summed vote) */
+    return lvl_hand_over(b, levels, gather_bytes);
 }
 
-/* the held build's post pass: 1 srt_levels_pred's source-major packed words with levels +
- * rel_pk_kernel, 2 its target-major words + a transpose + rel_pk_kernel, 0 the u8 level rows +
- * rel_tree_kernel */
-int srt_levels_pkw_ready(void) {
+/* the held build's post pass (see lvl_hand_over; SRT_LVL_POST_U8 when none is held) */
+srt_lvl_post_form srt_levels_pkw_ready(void) {
     const lvl_state* L = &g_lvl[srt_state_slot()];
-    return L->held ? L->pkw : 0;
+    return L->held ? L->post : SRT_LVL_POST_U8;
 }
 
-/* Canonical predecessors and their arc reliabilities of the held level build, target-major
- * (predT[t][sl], rT[t][sl], row stride ldp), as pred_cols*_kernel leave them for the transposes
- * and the reliability passes; ties != NULL adds the tied pairs. pred16: predT holds int16 (n <=
- * 32768: half the bytes of the predecessor slab and its transpose), else int32. */
-int srt_levels_pred(void* predT, int pred16, double* rT, size_t ldp, unsigned long long* ties,
+/* lvl_pred_kernel's words of type PT (int32, int16 or the packed u32), target-major */
+template <typename PT>
+static void lvl_pred_launch(const lvl_state* L, void* predT, double* rT, size_t ldp, unsigned long long* part,
+                            uint32_t* bkt, uint32_t* bcnt, int cap, hipStream_t st) {
+    lvl_pred_kernel<PT><<<lvl_grid((const void*)lvl_pred_kernel<PT>, L->nblk), 256, 0, st>>>(
+        L->n, L->nw, L->nchunk, L->row0, L->nrows, L->D, L->nblk, L->off, L->arcs, L->aoff, L->ar, L->rix,
+        L->lev, (PT*)predT, rT, ldp, part, bkt, bcnt, cap);
+}
+
+/* Canonical predecessors and their arc reliabilities of the held level build in the layout `out`
+ * (srt_device.h): target-major (predT[t][sl], rT[t][sl], row stride ldp), as pred_cols*_kernel
+ * leave them for the transposes and the reliability passes, or the packed words source-major,
+ * predT the rows pk[local source][target] of stride ldp (lvl_pred_rows_kernel; no tie count).
+ * ties != NULL adds the tied pairs. */
+int srt_levels_pred(void* predT, srt_lvl_pred_layout out, double* rT, size_t ldp, unsigned long long* ties,
                     int32_t* pn_over, int* pn_cap, hipStream_t st) {
-    /* pred16 == 2: the packed form (srt_levels_rtab); 3: the packed form source-major, predT the
-     * rows pk[local source][target] of stride ldp (lvl_pred_rows_kernel; no tie count) */
     lvl_state* L = &g_lvl[srt_state_slot()];
     if (!L->held) {
         srt_set_error("levels: no held level build for the predecessor pass");
@@ -3244,15 +3382,16 @@ int srt_levels_pred(void* predT, int pred16, double* rT, size_t ldp, unsigned lo
         SRT_HIPCHK(srt_malloc_async(&part, 1024 * sizeof(unsigned long long), st));
         SRT_HIPCHK(hipMemsetAsync(part, 0, 1024 * sizeof(unsigned long long), st));
     }
-    if (pred16 && L->n > 32768) {
+    const bool packed = out == SRT_LVL_PRED_PK_COLS || out == SRT_LVL_PRED_PK_ROWS;
+    if (out != SRT_LVL_PRED_I32 && L->n > 32768) {
         srt_set_error("levels: int16 predecessors need n <= 32768 (n = %d)", L->n);
         return SRT_E_ARG;
     }
-    if (pred16 >= 2 && !L->rix) {
+    if (packed && !L->rix) {
         srt_set_error("levels: the packed form needs the reliability table");
         return SRT_E_ARG;
     }
-    if (pred16 == 3 && (ties || L->D > 31 || (!L->apk && L->total > 0))) {
+    if (out == SRT_LVL_PRED_PK_ROWS && (ties || L->D > 31 || (!L->apk && L->total > 0))) {
         srt_set_error("levels: the source-major packed words take no tie count, at most 31 levels and "
                       "the build's arc words (pkw 1)");
         return SRT_E_ARG;
@@ -3262,21 +3401,18 @@ int srt_levels_pred(void* predT, int pred16, double* rT, size_t ldp, unsigned lo
      * share), few levels (a plane row is read per level: the first arc batch, D <= 8) and a
      * sparse Delta_1 (the histogram's capacity <= 1,024; past that the plane slices are dense
      * enough to gather). SRT_FORM bcap (the bucket capacity hook of the sparse kernels, which a
-     * level build does not otherwise read; the key budget of SRT_FORM is spent): k > 0 takes
-     * the pre-pass always, with buckets of min(k, 2,048) entries -- 2,048 cannot overflow, a
-     * small k makes the tests' overflowing buckets --, k < 0 never. Not with the tie count: a
-     * tied pair is seen only by walking the whole group. */
+     * level build does not otherwise read; the key budget of SRT_FORM is spent; as the build
+     * read it): k > 0 takes the pre-pass always, with buckets of min(k, 2,048) entries -- 2,048
+     * cannot overflow, a small k makes the tests' overflowing buckets --, k < 0 never. Not with
+     * the tie count: a tied pair is seen only by walking the whole group. */
     uint32_t *bkt = NULL, *bcnt = NULL;
     int cap = 0;
     *pn_cap = 0;
-    {
-        const int fcap = srt_form_int("bcap", 0);
-        if (fcap > 0)
-            cap = min(fcap, 2048);
-        else if (fcap == 0 && L->nw >= LVL_NEAR_MIN_NW && L->D <= LVL_BATCH && L->pn_cap <= 1024)
-            cap = L->pn_cap;
-        if (ties || !pn_over || L->D < 2 || L->nw > LVL_NEAR_NW) cap = 0;
-    }
+    if (L->fbcap > 0)
+        cap = min(L->fbcap, 2048);
+    else if (L->fbcap == 0 && L->nw >= LVL_NEAR_MIN_NW && L->D <= LVL_BATCH && L->pn_cap <= 1024)
+        cap = L->pn_cap;
+    if (ties || !pn_over || L->D < 2 || L->nw > LVL_NEAR_NW) cap = 0;
     if (cap) {
         const size_t units = (size_t)L->n * L->nchunk;
         int ok = 1; /* no room for the buckets: the walk as it is (pred_near reports 0) */
@@ -3291,7 +3427,7 @@ int srt_levels_pred(void* predT, int pred16, double* rT, size_t ldp, unsigned lo
         SRT_HIPCHK(hipGetLastError());
         *pn_cap = cap;
     }
-    if (pred16 == 3) { /* narrow units: the packed words straight into the source-major rows */
+    if (out == SRT_LVL_PRED_PK_ROWS) { /* narrow units: the packed words straight into the rows */
         constexpr int TPW = 4, NWV = 4; /* 16 targets x 512 sources per workgroup of 256 threads */
         const auto kern = lvl_pred_rows_kernel<TPW, NWV, 8>;
         const unsigned ntg = (unsigned)srt_ceil_div(L->n, TPW * NWV);
@@ -3302,25 +3438,18 @@ int srt_levels_pred(void* predT, int pred16, double* rT, size_t ldp, unsigned lo
          * C4 on one GPU takes 4 and on N = 2 takes 2, at 18 rounds each; N >= 4 keeps 1).
          * SRT_FORM pkw=3 / 4 (tests, A/B): one sub-chunk / whole chunks at any share. */
         const unsigned full = lvl_grid((const void*)kern, ~0u, 0, NWV * 64);
-        const int fpkw = srt_form_int("pkw", 1);
-        unsigned S = fpkw == 3 ? 1u : 4u;
-        while (fpkw != 4 && S > 1 && ntg * ((nsub + S - 1) / S) < LVL_ROWS_MIN_ROUNDS * full) S >>= 1;
+        unsigned S = L->fpkw == 3 ? 1u : 4u;
+        while (L->fpkw != 4 && S > 1 && ntg * ((nsub + S - 1) / S) < LVL_ROWS_MIN_ROUNDS * full) S >>= 1;
         const unsigned nunit = ntg * ((nsub + S - 1) / S);
         kern<<<min(full, nunit), NWV * 64, 0, st>>>(
             L->n, L->nw, L->nchunk, L->row0, L->nrows, L->D, ntg, nunit, (int)S, L->off, L->arcs, L->aoff,
             L->apk, L->lev, (uint32_t*)predT, ldp, bkt, bcnt, cap);
-    } else if (pred16 == 2)
-        lvl_pred_kernel<uint32_t><<<lvl_grid((const void*)lvl_pred_kernel<uint32_t>, L->nblk), 256, 0, st>>>(
-            L->n, L->nw, L->nchunk, L->row0, L->nrows, L->D, L->nblk, L->off, L->arcs, L->aoff, L->ar,
-            L->rix, L->lev, (uint32_t*)predT, rT, ldp, part, bkt, bcnt, cap);
-    else if (pred16)
-        lvl_pred_kernel<int16_t><<<lvl_grid((const void*)lvl_pred_kernel<int16_t>, L->nblk), 256, 0, st>>>(
-            L->n, L->nw, L->nchunk, L->row0, L->nrows, L->D, L->nblk, L->off, L->arcs, L->aoff, L->ar,
-            L->rix, L->lev, (int16_t*)predT, rT, ldp, part, bkt, bcnt, cap);
+    } else if (out == SRT_LVL_PRED_PK_COLS)
+        lvl_pred_launch<uint32_t>(L, predT, rT, ldp, part, bkt, bcnt, cap, st);
+    else if (out == SRT_LVL_PRED_I16)
+        lvl_pred_launch<int16_t>(L, predT, rT, ldp, part, bkt, bcnt, cap, st);
     else
-        lvl_pred_kernel<int32_t><<<lvl_grid((const void*)lvl_pred_kernel<int32_t>, L->nblk), 256, 0, st>>>(
-            L->n, L->nw, L->nchunk, L->row0, L->nrows, L->D, L->nblk, L->off, L->arcs, L->aoff, L->ar,
-            L->rix, L->lev, (int32_t*)predT, rT, ldp, part, bkt, bcnt, cap);
+        lvl_pred_launch<int32_t>(L, predT, rT, ldp, part, bkt, bcnt, cap, st);
     SRT_HIPCHK(hipGetLastError());
     if (ties) {
         lvl_sum_kernel<<<1, 1024, 0, st>>>(part, 1024, ties);

@@ -166,24 +166,36 @@ int srt_fw16_build(int n, int ld, int row0, int nrows, const uint32_t* w_rows, u
 int srt_levels_build(const srt_comm* comm, int n, int ld, int row0, int nrows, int directed,
                      const uint32_t* w_rows, const double* r_rows, uint32_t* lat_rows, double fw_ms,
                      hipStream_t st, evpool_t* evp, int* levels, int64_t* gather_bytes);
-/* predecessors (int16 when pred16, else int32) + arc reliabilities of the held level build
- * (target-major, row stride ldp). *pn_cap: the bucket capacity of lvl_pred_near_kernel's pre-pass
- * (0: not taken); it adds its overflowed buckets to the device word pn_over. pred16 = 2: packed
- * words, target-major; pred16 = 3: the same words source-major, predT[local source][target] with
- * row stride ldp (no transpose after it; ties must be NULL) */
-int srt_levels_pred(void* predT, int pred16, double* rT, size_t ldp, unsigned long long* ties,
-                    int32_t* pn_over, int* pn_cap, hipStream_t st);
-/* nonzero when the held level build's post pass is the packed-word form (pred | reliability
- * index << 16 | level << 27 per pair, then rel_pk_kernel writes the u32 rows too): 1 the words
- * source-major (srt_levels_pred with pred16 = 3), 2 target-major (pred16 = 2) and one transpose;
- * 0: the u8 level rows + srt_levels_pred + rel_tree_kernel */
-int srt_levels_pkw_ready(void);
+/* what srt_levels_pred writes: predecessors + arc reliabilities (rT) target-major with row stride
+ * ldp, or one packed word per pair (pred | reliability index << 16 | level << 27, no rT) */
+typedef enum {
+    SRT_LVL_PRED_I32 = 0,     /* int32 predecessors + f64 reliabilities, target-major */
+    SRT_LVL_PRED_I16 = 1,     /* int16 predecessors (n <= 32768) + f64 reliabilities, target-major */
+    SRT_LVL_PRED_PK_COLS = 2, /* packed words, target-major (needs srt_levels_rtab) */
+    SRT_LVL_PRED_PK_ROWS = 3, /* packed words source-major, predT[local source][target] with row
+                               * stride ldp: no transpose after it; ties must be NULL */
+} srt_lvl_pred_layout;
+/* the post pass a held level build was made for */
+typedef enum {
+    SRT_LVL_POST_U8 = 0,      /* the u8 level rows + srt_levels_pred + rel_tree_kernel */
+    SRT_LVL_POST_PK_ROWS = 1, /* packed words source-major (SRT_LVL_PRED_PK_ROWS), then rel_pk_kernel,
+                               * which writes the u32 rows too */
+    SRT_LVL_POST_PK_COLS = 2, /* packed words target-major (SRT_LVL_PRED_PK_COLS), one transpose,
+                               * rel_pk_kernel */
+} srt_lvl_post_form;
+/* predecessors + arc reliabilities of the held level build in the layout `out`. *pn_cap: the
+ * bucket capacity of lvl_pred_near_kernel's pre-pass (0: not taken); it adds its overflowed
+ * buckets to the device word pn_over. */
+int srt_levels_pred(void* predT, srt_lvl_pred_layout out, double* rT, size_t ldp,
+                    unsigned long long* ties, int32_t* pn_over, int* pn_cap, hipStream_t st);
+/* the held level build's post pass (SRT_LVL_POST_U8 when none is held) */
+srt_lvl_post_form srt_levels_pkw_ready(void);
 /* frees the held level build (stream-ordered) */
 void srt_levels_release(hipStream_t st);
 /* the held build's u8 distance rows (nrows x ld, 0 on the diagonal), NULL if none */
 const uint8_t* srt_levels_l8(void);
 /* the held level build's distinct arc reliabilities (the packed post pass: predecessor | index << 16
- * words, srt_levels_pred with pred16 = 2); NULL (ntab 0) when the build keeps the f64 form */
+ * words, SRT_LVL_PRED_PK_COLS / PK_ROWS); NULL (ntab 0) when the build keeps the f64 form */
 const double* srt_levels_rtab(int* ntab);
 /* the diagonal rule of the held build's rows (keys from its row reads); *applied = 0 when it kept
  * none (directed builds: dense_diag_kernel) */
