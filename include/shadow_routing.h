@@ -87,13 +87,14 @@ typedef struct srt_build_stats {
                           * Dense: the distance encoding the build finished with: 12 = bit-parallel
                           * Dial levels (no FW rounds; levels.hip), (9: retired 256-pivot
                           * sharded rounds), 8 = u16
-                          * f16-compare row-sharded symmetric rounds of 128 pivots (N > 1;
-                          * 4 with SRT_FORM shkb=64), 7 = 5 with
-                          * 256-pivot rounds (four panels per C-tile residency), 6 = 5 with
-                          * 128-pivot rounds (two panels per C-tile residency), 5 = 4 on two
-                          * update streams (one GPU, n >= 8192), 4 = u16 with
-                          * f16-compare mins, upper-triangle rounds (undirected; one GPU, or
-                          * row-sharded kept tiles in 64-pivot rounds),
+                          * f16-compare row-sharded symmetric rounds of 128 pivots (N > 1),
+                          * 7 = 4 on two update streams with
+                          * 256-pivot rounds (four panels per C-tile residency; one GPU,
+                          * ld >= 8192), 6 = the same with
+                          * 128-pivot rounds (two panels per C-tile residency), (5: retired
+                          * 64-pivot rounds on two update streams), 4 = u16 with
+                          * f16-compare mins, upper-triangle 64-pivot rounds (undirected, one
+                          * GPU),
                           * 3 = u16 f16-compare (cap 0x3DFF), 2 = u16 pk_min (cap 0x7FFF), 1 = u32 */
     int32_t count_ties;  /* input: 1 = count tied pairs (below) */
     int64_t tied_pairs;  /* pairs (s, t), s != t, whose smallest D[s][u] over the tight

@@ -2772,16 +2772,11 @@ int srt_dense_build_device_ms(int32_t n, int32_t ld, int32_t directed, const uin
             evp->used = 0;
             evp->group = 2;
         }
-        int sym = !directed;
-        rc = srt_fw16_build(n, ld, 0, ld, w, lat, st, evp, NULL, NULL, NULL, 0, fm, &sym, &exact);
+        int fw_enc = SRT_DENC_U32;
+        rc = srt_fw16_build(n, ld, 0, ld, w, lat, st, evp, NULL, NULL, NULL, 0, fm, !directed,
+                            &fw_enc, &exact);
         if (rc) return rc;
-        if (exact)
-            enc = !fm ? SRT_DENC_U16
-                      : sym == 5 ? SRT_DENC_SQUARE
-                      : sym == 4 ? SRT_DENC_F16CMP_SYM256
-                      : sym == 3 ? SRT_DENC_F16CMP_SYM128
-                      : sym == 2 ? SRT_DENC_F16CMP_SYM2
-                                 : sym ? SRT_DENC_F16CMP_SYM : SRT_DENC_F16CMP;
+        if (exact) enc = fw_enc;
     }
     if (!exact) { /* u32 path: ld not a multiple of 128, or a distance reached 0x7FFF quanta */
         if (evp) {
@@ -2934,7 +2929,7 @@ int srt_dense_build_sharded_ms(srt_comm* comm, int32_t n, int32_t ld, int32_t di
             rc = srt_fw16_build_sym_sharded(comm, n, ld, b, nr, w_rows, lat_rows, st, evp, &exact);
         else
             rc = srt_fw16_build(n, ld, b, nr, w_rows, lat_rows, st, evp, shard_owner,
-                                R > 1 ? shard_bcast : NULL, &ctx, me, fm, NULL, &exact);
+                                R > 1 ? shard_bcast : NULL, &ctx, me, fm, 0, NULL, &exact);
         if (rc) return rc;
         if (R > 1) { /* every rank must agree before falling back to a wider encoding */
             int32_t* flag = ws->cnt;
@@ -2944,11 +2939,7 @@ int srt_dense_build_sharded_ms(srt_comm* comm, int32_t n, int32_t ld, int32_t di
             SRT_HIPCHK(hipStreamSynchronize(st));
         }
         if (exact)
-            enc = fm ? (sym ? (srt_fw16_sharded_round_pivots() == 256   ? SRT_DENC_F16CMP_SYMSH256
-                               : srt_fw16_sharded_round_pivots() == 128 ? SRT_DENC_F16CMP_SYMSH128
-                                                                        : SRT_DENC_F16CMP_SYM)
-                            : SRT_DENC_F16CMP)
-                     : SRT_DENC_U16;
+            enc = fm ? (sym ? SRT_DENC_F16CMP_SYMSH128 : SRT_DENC_F16CMP) : SRT_DENC_U16;
     }
     if (!exact) {
         if (evp) {

@@ -30,6 +30,9 @@
  */
 #include "srt_device.h"
 
+#include <algorithm>
+#include <vector>
+
 typedef unsigned short u16;
 typedef u16 u16x2 __attribute__((ext_vector_type(2)));
 
@@ -500,35 +503,21 @@ static __host__ __device__ __forceinline__ bool sym_kept(int I, int J) {
 /* SYM: only upper-triangle tiles (I <= J, grid T(T+1)/2) -- an undirected graph's distance
  * matrix stays symmetric through every round, so the lower triangle is the transpose and half the
  * relaxations are skipped; A comes from the pivot panel transposed.
- * XM (row-sharded SYM, D = the rank's rows from tile row i0 = tb, te = end tile row, skip = the
- * tile row K1 of the next pivot block or -1): 3 = the kept tiles of tile row K1 (block b < T: J =
- * b) and of tile column K1 in the rank's rows (b >= T: I = tb + b - T), which the next pivot
- * panel is assembled from; 4 = the rank's kept-tile list tl minus those; 5 = the whole list;
- * 6 = (one GPU, two update streams) the upper-triangle tiles of tile row / column K1 whose
- * I + J has the parity i0; 7 / 8 = mode 3 restricted to even / odd J (the sharded rounds' two
- * update streams). */
+ * XM (tile-list modes: D = the rows from tile row i0 -- 0 on one GPU, the rank's tb when
+ * row-sharded -- and skip = the tile row K1 of the next round's pivot block or -1): 4 = the
+ * tile list tl minus the cross (tile row and column) of K1; 5 = the whole list; 6 = (one GPU, two
+ * update streams) the upper-triangle tiles of the cross of K1 whose I + J has the parity i0.
+ * Modes 9, 13 and 20 are decoded in fwq_update_kernel itself. */
 /* The tile (I, J) the calling block of a mode-XM launch updates and its local tile row Iloc;
  * false when the block has nothing to do (the modes: the comment above). */
 template <bool SYM, int XM>
 static __device__ __forceinline__ bool fw_tile_of(int ncol_tiles, int i0, int skip,
-                                                  const uint32_t* __restrict__ tl, int te, int& I,
+                                                  const uint32_t* __restrict__ tl, int /*te*/, int& I,
                                                   int& J, int& Iloc) {
     const int nb = gridDim.x;
     const int per = nb >> 3;
     const int bid = (nb & 7) == 0 ? (blockIdx.x & 7) * per + (blockIdx.x >> 3) : blockIdx.x;
-    if (XM == 3 || XM == 7 || XM == 8) {
-        if (blockIdx.x < ncol_tiles) {
-            J = blockIdx.x;
-            I = skip;
-            if (I < i0 || I >= te || !sym_kept(I, J)) return false;
-        } else {
-            I = i0 + (int)blockIdx.x - ncol_tiles;
-            J = skip;
-            if (I >= te || I == skip || !sym_kept(I, J)) return false;
-        }
-        if (XM != 3 && (J & 1) != XM - 7) return false; /* two update streams: tile set J mod 2 */
-        Iloc = I - i0;
-    } else if (XM == 6) { /* one GPU, upper triangle: the cross of K1 restricted to I + J = i0 mod 2 */
+    if (XM == 6) { /* one GPU, upper triangle: the cross of K1 restricted to I + J = i0 mod 2 */
         I = min((int)blockIdx.x, skip);
         J = max((int)blockIdx.x, skip);
         if (((I + J) & 1) != i0) return false;
@@ -662,7 +651,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     const uint32_t* __restrict__ tl, int te, int prev = -1, u16* __restrict__ outq = nullptr) {
     __shared__ __attribute__((aligned(16))) uint32_t sA[UKC / 2 * 128 * 2];
     __shared__ __attribute__((aligned(16))) u16 sB[UKC * UBS];
-    if constexpr (XM == 3 || XM == 6 || XM == 7 || XM == 8 || XM == 9 || XM == 13)
+    if constexpr (XM == 6 || XM == 9 || XM == 13)
         FW_CHAIN_PRIO(); /* next-row tiles */
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     int I, J, Iloc;
@@ -1142,11 +1131,13 @@ __global__ __launch_bounds__(256) void sym_fill_local_kernel(u16* __restrict__ D
 }
 
 #ifndef SRT_FW16_DEVICE_ONLY
-#define FW_UPDATE(SYMV, XMV, GRID, STREAM, ...) \
-    fwq_update_kernel<SYMV, XMV><<<(GRID), 512, 0, (STREAM)>>>(__VA_ARGS__)
 /* ---- orchestration --------------------------------------------------------------------------- *
- * Lookahead schedule (one row shard per rank; a single GPU is the 1-rank case). Round k uses the
- * 64-row pivot panel P_k (owner: in place in its rows; others: a double-buffered receive panel).
+ * Three schedules. The all-tile rounds of srt_fw16_build (directed graphs, the pk_min mix, SRT_FORM
+ * sym=0) are the lookahead schedule below; an undirected graph on one GPU takes the
+ * upper-triangle rounds of fw16_build_sym, on two or more ranks the row-sharded kept-tile rounds
+ * of srt_fw16_build_sym_sharded.
+ * Lookahead schedule (one row shard per rank). Round k uses the 64-row pivot panel P_k (owner: in
+ * place in its rows; others: a double-buffered receive panel).
  * Main stream st:      wait P_k ready -> pivot-column tiles of k -> update k
  * Critical stream cs:  diagonal closure + pivot-row panel of k+1 -> broadcast P_k+1 -> P_k+1 ready
  * On the owner of k+1 the update of round k is split: the 128-row tile row holding block k+1 goes
@@ -1154,17 +1145,47 @@ __global__ __launch_bounds__(256) void sym_fill_local_kernel(u16* __restrict__ D
  * overlap the panel work and the RCCL broadcast. A receive panel is overwritten only after the
  * update that last read it (round k-1) has finished.
  * Without a broadcast to hide (one GPU) the split and the cross-stream events cost more than the
- * overlap returns (C2: 1.01 -> 1.34 ms), so the single-GPU build runs the same rounds on one stream
- * in order; SRT_FORM lookahead=1 forces the two-stream schedule (tests exercise it on one GPU). */
+ * overlap returns (C2: 1.01 -> 1.34 ms), so there the same rounds run on one stream in order. */
 /* per-device u16 working matrix of the last build (rows of the shard, ld columns); the dense
  * post pass reads it transposed for the predecessor search (half the bytes of the u32 table) */
 static u16* fw16_bufs[SRT_STATE_SLOTS];
-static size_t fw16_caps[SRT_STATE_SLOTS]; /* elements allocated in fw16_bufs (shared by both build forms) */
+static size_t fw16_caps[SRT_STATE_SLOTS]; /* elements allocated in fw16_bufs (shared by every build form) */
 static int* fw16_flags[SRT_STATE_SLOTS];
 static int fw16_small[SRT_STATE_SLOTS]; /* last build: every real distance <= 254 quanta */
 int srt_fw16_small(void) { return fw16_small[srt_state_slot()]; }
-static thread_local int g_sharded_rp = 64; /* pivots per round of this thread's last sharded build */
 const uint16_t* srt_fw16_matrix(void) { return fw16_bufs[srt_state_slot()]; }
+
+/* the slot's working matrix with room for `need` u16 values, and its two flag words */
+static int fw16_ensure(int dev, size_t need) {
+    if (fw16_caps[dev] < need || !fw16_bufs[dev]) {
+        if (fw16_bufs[dev]) SRT_HIPCHK(hipFree(fw16_bufs[dev]));
+        fw16_bufs[dev] = NULL;
+        fw16_caps[dev] = 0;
+        SRT_HIPCHK(hipMalloc(&fw16_bufs[dev], need * sizeof(u16)));
+        fw16_caps[dev] = need;
+    }
+    if (!fw16_flags[dev]) SRT_HIPCHK(hipMalloc(&fw16_flags[dev], 2 * sizeof(int)));
+    return SRT_OK;
+}
+
+/* the tail of every build: rows row0.. of d widened into the u32 table, then the two flags read
+ * back -- *exact = no real distance reached cap, fw16_small = every one is <= 254 quanta */
+static int fw16_finish(int n, int ld, int row0, int nrows, const u16* d, uint32_t* lat, uint32_t cap,
+                       hipStream_t st, int* exact) {
+    const int dev = srt_state_slot();
+    int* flags = fw16_flags[dev];
+    SRT_HIPCHK(hipMemsetAsync(flags, 0, 2 * sizeof(int), st));
+    if (nrows > 0)
+        fw16_finish_kernel<<<dim3(srt_ceil_div(ld, 2048), nrows), 256, 0, st>>>(n, ld, row0, d, lat,
+                                                                               flags, cap);
+    SRT_HIPCHK(hipGetLastError());
+    int hf[2] = {0, 0};
+    SRT_HIPCHK(hipMemcpyAsync(hf, flags, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+    SRT_HIPCHK(hipStreamSynchronize(st));
+    *exact = hf[0] ? 0 : 1;
+    fw16_small[dev] = hf[1] ? 0 : 1;
+    return SRT_OK;
+}
 
 typedef struct {
     hipStream_t cs;
@@ -1210,776 +1231,470 @@ static int sched_get(fw16_sched** out, int dev) {
     return SRT_OK;
 }
 
-/* Upper-triangle blocked FW for an undirected graph on one GPU (f16-compare kernels). */
+/* ---- upper-triangle rounds on one GPU -------------------------------------------------------- */
+/* close panel k0 on stream s (one GPU, the whole matrix d): the diagonal block, the pivot-row
+ * panel P_k0 (in place in rows k0..), and the panel's columns below k0 refreshed from the rows
+ * that are already final. The caller checks the launches. */
+static void fw16_close_panel(u16* d, int ld, int k0, hipStream_t s) {
+    const int nb = ld / KB;
+    u16* P = d + (size_t)k0 * ld;
+    fw16_diag_kernel<true><<<1, 256, 0, s>>>(P, ld, k0);
+    fw16_panel_kernel<true, true><<<2 * nb, 256, 0, s>>>(d, ld, 0, nb, P, k0, nb, 1, 1);
+    if (k0 > 0) fw16_refresh_kernel<<<k0 / KB, 256, 0, s>>>(d, ld, k0);
+}
+
+/* the two static tile sets of the two-stream rounds (upper-triangle tiles by the parity of
+ * I + J, row-major) as device lists: tls[p], nset[p] */
+static int sym_tile_sets(fw16_sched* sc, int T, hipStream_t st, const uint32_t* tls[2], int nset[2]) {
+    const size_t ntri = (size_t)T * (T + 1) / 2;
+    std::vector<uint32_t> h;
+    h.reserve(ntri);
+    nset[0] = nset[1] = 0;
+    for (int p = 0; p < 2; p++)
+        for (int I = 0; I < T; I++)
+            for (int J = I; J < T; J++)
+                if (((I + J) & 1) == p) {
+                    h.push_back(((uint32_t)I << 16) | (uint32_t)J);
+                    nset[p]++;
+                }
+    if (!sc->tl2 || sc->tl2_cap < ntri) {
+        if (sc->tl2) SRT_HIPCHK(hipFree(sc->tl2));
+        sc->tl2 = NULL;
+        SRT_HIPCHK(hipMalloc(&sc->tl2, ntri * sizeof(uint32_t)));
+        sc->tl2_cap = ntri;
+    }
+    /* pageable source: finished before the host list goes */
+    SRT_HIPCHK(hipMemcpyAsync(sc->tl2, h.data(), ntri * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    SRT_HIPCHK(hipStreamSynchronize(st));
+    tls[0] = sc->tl2;
+    tls[1] = sc->tl2 + nset[0];
+    return SRT_OK;
+}
+
+/* RP-pivot rounds, RP = 128 or 256: round j takes pivot blocks RP / KB * j .., which are the
+ * RP / 128 tile rows from R0 = RP / 128 * j, and every C tile stays resident for all of the
+ * round's panels (RP / UKC stages of 32 pivots), which divides the per-pivot C loads, row sums
+ * and stores and the bulk launches by RP / 64.
+ * Chain stream cs, round j (sym_chain): close P_a, apply it to the cross of tile R0 (its row and
+ * column, XM 9), close P_b; at 256 go on: apply P_a and P_b to the cross of R0 + 1, close P_c,
+ * apply it to the cross of R0 + 1, close P_d; then ready[j].
+ * Update stream p, round j (after ready[j]): the crosses of the next round's tile rows with all
+ * the round's panels (XM 6 / 13), then the rest with all of them (XM 4), whose tiles in the
+ * crosses of this round's tile rows start past the panels the chain already applied
+ * (fwq_update_kernel prev). The next round's crosses are left out of the rest and updated first,
+ * so cs can close P_a of round j + 1 under the rest; cs's cross updates touch no tile of the rest
+ * launch still running (round j - 1 leaves out the crosses of round j). */
+template <int RP>
+static int sym_chain(fw16_sched* sc, u16* d, int ld, int j) {
+    const int T = ld / 128, ka = j * RP, R0 = j * (RP / 128);
+    hipStream_t cs = sc->cs;
+    u16* Pa = d + (size_t)ka * ld;
+    fw16_close_panel(d, ld, ka, cs);
+    fwq_update_kernel<true, 9, 2><<<T, 512, 0, cs>>>(d, ld, Pa, ka, T, 0, R0, nullptr, 0, -1);
+    fw16_close_panel(d, ld, ka + KB, cs);
+    if constexpr (RP == 256) {
+        const int kc = ka + 2 * KB;
+        fwq_update_kernel<true, 9, 4><<<T, 512, 0, cs>>>(d, ld, Pa, ka, T, 0, R0 + 1, nullptr, 0, -1);
+        fw16_close_panel(d, ld, kc, cs);
+        fwq_update_kernel<true, 9, 2><<<T, 512, 0, cs>>>(d, ld, d + (size_t)kc * ld, kc, T, 0, R0 + 1,
+                                                       nullptr, 0, -1);
+        fw16_close_panel(d, ld, kc + KB, cs);
+    }
+    SRT_HIPCHK(hipGetLastError());
+    SRT_HIPCHK(hipEventRecord(sc->ready[j & 1], cs));
+    return SRT_OK;
+}
+
+template <int RP>
+static int sym_rounds(fw16_sched* sc, u16* d, int ld, hipStream_t st, evpool_t* evp,
+                      const uint32_t* const tls[2], const int nset[2]) {
+    constexpr int TR = RP / 128, NST = RP / UKC, XNEXT = RP == 256 ? 13 : 6;
+    const int T = ld / 128, R = T / TR;
+    hipStream_t cs = sc->cs, ss[2] = {st, sc->xs};
+    int rc;
+    if ((rc = sym_chain<RP>(sc, d, ld, 0))) return rc;
+    for (int j = 0; j < R; ++j) {
+        const int ka = j * RP, K1 = TR * (j + 1);
+        u16* Pa = d + (size_t)ka * ld;
+        const bool next = j + 1 < R;
+        for (int p = 0; p < 2; p++) {
+            SRT_HIPCHK(hipStreamWaitEvent(ss[p], sc->ready[j & 1], 0));
+            if (next) {
+                fwq_update_kernel<true, XNEXT, NST><<<TR * T, 512, 0, ss[p]>>>(d, ld, Pa, ka, T, p, K1,
+                                                                            nullptr, 0, -1);
+                SRT_HIPCHK(hipEventRecord(sc->e_set[j & 1][p], ss[p]));
+            }
+        }
+        if (next) {
+            SRT_HIPCHK(hipStreamWaitEvent(cs, sc->e_set[j & 1][0], 0));
+            SRT_HIPCHK(hipStreamWaitEvent(cs, sc->e_set[j & 1][1], 0));
+            if ((rc = sym_chain<RP>(sc, d, ld, j + 1))) return rc;
+        }
+        /* timed as one unit: the two rest-of-round launches, from the first start to the
+         * last end (evpool group 4: start A, start B, end A, end B) */
+        const int e0 = evp ? evp->used : 0;
+        if (evp && next) {
+            evp->group = 4;
+            evp->used += 4;
+        }
+        for (int p = 0; p < 2; p++) {
+            if (evp && next) SRT_HIPCHK(hipEventRecord(evp->ev[e0 + p], ss[p]));
+            if (next)
+                fwq_update_kernel<true, 4, NST><<<(unsigned)nset[p], 512, 0, ss[p]>>>(
+                    d, ld, Pa, ka, T, 0, K1, tls[p], T, TR * j);
+            else
+                fwq_update_kernel<true, 5, NST><<<(unsigned)nset[p], 512, 0, ss[p]>>>(
+                    d, ld, Pa, ka, T, 0, -1, tls[p], T, TR * j);
+            if (evp && next) SRT_HIPCHK(hipEventRecord(evp->ev[e0 + 2 + p], ss[p]));
+        }
+        SRT_HIPCHK(hipGetLastError());
+    }
+    return SRT_OK;
+}
+
 /* Upper-triangle blocked FW for an undirected graph on one GPU (f16-compare kernels).
- * two: the upper-triangle tiles are split by the parity of I + J into two static sets, each
- * updated by its own stream (st, xs) every round, while the high-priority stream cs closes the
- * next diagonal block, builds the next panel and refreshes it as soon as both streams have
- * updated their tiles of the next pivot block's tile row and column (launched first). A stream
+ * rp = 64: 64-pivot rounds on one stream, in order. rp = 128 / 256: the upper-triangle tiles are
+ * split by the parity of I + J into two static sets, each updated by its own stream (st, xs)
+ * every round, while the high-priority stream cs closes the next round's panels as soon as both
+ * streams have updated their tiles of the next pivot tile rows' crosses (launched first). A stream
  * depends only on its own previous launches and on the panel, so one stream's next round starts
  * in the other's tail and the panel work overlaps the update. A stream may then read pivot rows
  * that the other stream has already relaxed in the next round: those values are still lengths
  * of real paths, no larger than the round requires, so the result is the same exact matrix. */
 static int fw16_build_sym(int n, int ld, const uint32_t* w, uint32_t* lat, hipStream_t st,
-                          evpool_t* evp, int* exact, bool two, int round_pivots) {
-    const bool r128 = round_pivots == 128, r256 = round_pivots == 256;
+                          evpool_t* evp, int* exact, int rp) {
     const int dev = srt_state_slot(); /* the device, or this virtual rank's slot */
-    size_t* caps = fw16_caps;
-    int** flags = fw16_flags;
-    const size_t need = (size_t)ld * ld;
-    if (caps[dev] < need || !fw16_bufs[dev]) {
-        if (fw16_bufs[dev]) SRT_HIPCHK(hipFree(fw16_bufs[dev]));
-        fw16_bufs[dev] = NULL;
-        caps[dev] = 0;
-        SRT_HIPCHK(hipMalloc(&fw16_bufs[dev], need * sizeof(u16)));
-        caps[dev] = need;
-    }
-    if (!flags[dev]) SRT_HIPCHK(hipMalloc(&flags[dev], 2 * sizeof(int)));
+    int rc = fw16_ensure(dev, (size_t)ld * ld);
+    if (rc) return rc;
     u16* d = fw16_bufs[dev];
     fw16_init_kernel<<<dim3(srt_ceil_div(ld, 2048), ld), 256, 0, st>>>(n, ld, 0, w, d, CAP_F);
     SRT_HIPCHK(hipGetLastError());
     const int nb = ld / KB, T = ld / 128;
-    const int ntri = T * (T + 1) / 2;
-    if (!two) {
+    if (rp == 64) {
+        const int ntri = T * (T + 1) / 2;
         for (int k0 = 0; k0 < ld; k0 += KB) {
-            u16* P = d + (size_t)k0 * ld;
-            fw16_diag_kernel<true><<<1, 256, 0, st>>>(P, ld, k0);
-            fw16_panel_kernel<true, true><<<2 * nb, 256, 0, st>>>(d, ld, 0, nb, P, k0, nb, 1, 1);
-            if (k0 > 0) fw16_refresh_kernel<<<k0 / KB, 256, 0, st>>>(d, ld, k0);
+            fw16_close_panel(d, ld, k0, st);
             if (evp) SRT_HIPCHK(hipEventRecord(evp->ev[evp->used++], st));
-            FW_UPDATE(true, 0, ntri, st, d, ld, P, k0, T, 0, -1, nullptr, 0);
+            fwq_update_kernel<true, 0, 2><<<ntri, 512, 0, st>>>(d, ld, d + (size_t)k0 * ld, k0, T, 0, -1,
+                                                              nullptr, 0);
             if (evp) SRT_HIPCHK(hipEventRecord(evp->ev[evp->used++], st));
             SRT_HIPCHK(hipGetLastError());
         }
     } else {
         fw16_sched* sc;
-        int rc = sched_get(&sc, dev);
-        if (rc) return rc;
-        hipStream_t cs = sc->cs, xs = sc->xs;
-        /* the two tile sets, row-major, as device lists */
-        uint32_t* h = (uint32_t*)malloc((size_t)ntri * sizeof(uint32_t));
-        if (!h) return SRT_E_NOMEM;
-        int nset[2] = {0, 0};
-        for (int p = 0, o = 0; p < 2; p++)
-            for (int I = 0; I < T; I++)
-                for (int J = I; J < T; J++)
-                    if (((I + J) & 1) == p) {
-                        h[o++] = ((uint32_t)I << 16) | (uint32_t)J;
-                        nset[p]++;
-                    }
-        if (!sc->tl2 || sc->tl2_cap < (size_t)ntri) {
-            if (sc->tl2) SRT_HIPCHK(hipFree(sc->tl2));
-            sc->tl2 = NULL;
-            SRT_HIPCHK(hipMalloc(&sc->tl2, (size_t)ntri * sizeof(uint32_t)));
-            sc->tl2_cap = (size_t)ntri;
-        }
-        const hipError_t ce = hipMemcpyAsync(sc->tl2, h, (size_t)ntri * sizeof(uint32_t),
-                                             hipMemcpyHostToDevice, st);
-        const hipError_t se = ce == hipSuccess ? hipStreamSynchronize(st) : ce;
-        free(h);
-        SRT_HIPCHK(se);
-        const uint32_t* tls[2] = {sc->tl2, sc->tl2 + nset[0]};
-        hipStream_t ss[2] = {st, xs};
-        auto produce = [&](int k) -> int {
-            const int k0 = k * KB;
-            u16* P = d + (size_t)k0 * ld;
-            fw16_diag_kernel<true><<<1, 256, 0, cs>>>(P, ld, k0);
-            fw16_panel_kernel<true, true><<<2 * nb, 256, 0, cs>>>(d, ld, 0, nb, P, k0, nb, 1, 1);
-            if (k0 > 0) fw16_refresh_kernel<<<k0 / KB, 256, 0, cs>>>(d, ld, k0);
-            SRT_HIPCHK(hipGetLastError());
-            SRT_HIPCHK(hipEventRecord(sc->ready[k & 1], cs));
-            return SRT_OK;
-        };
+        if ((rc = sched_get(&sc, dev))) return rc;
+        const uint32_t* tls[2];
+        int nset[2];
+        if ((rc = sym_tile_sets(sc, T, st, tls, nset))) return rc;
         SRT_HIPCHK(hipEventRecord(sc->init_done, st));
-        SRT_HIPCHK(hipStreamWaitEvent(cs, sc->init_done, 0));
-        SRT_HIPCHK(hipStreamWaitEvent(xs, sc->init_done, 0));
-        if (r256) {
-            /* 256-pivot rounds (pivot blocks a..d = 4j..4j+3: tile rows R0 = 2j, R1 = 2j + 1):
-             * every C tile stays resident for four panels (eight 32-pivot stages). Chain stream cs,
-             * per round j: close P_a, apply it to the cross of R0; close P_b, apply P_a and P_b to
-             * the cross of R1; close P_c, apply it to the cross of R1; close P_d -> ready[j].
-             * Update stream p, per round j (after ready[j]): the crosses of the next round's tile
-             * rows with all four panels, then the rest, whose tiles in the crosses of R0 / R1 start
-             * past the panels the chain already applied (fwq_update_kernel prev). */
-            auto closep = [&](int k0) -> int {
-                u16* P = d + (size_t)k0 * ld;
-                fw16_diag_kernel<true><<<1, 256, 0, cs>>>(P, ld, k0);
-                fw16_panel_kernel<true, true><<<2 * nb, 256, 0, cs>>>(d, ld, 0, nb, P, k0, nb, 1, 1);
-                if (k0 > 0) fw16_refresh_kernel<<<k0 / KB, 256, 0, cs>>>(d, ld, k0);
-                SRT_HIPCHK(hipGetLastError());
-                return SRT_OK;
-            };
-            auto produce4 = [&](int j) -> int {
-                const int ka = 4 * j * KB, R0 = 2 * j;
-                int rc2;
-                if ((rc2 = closep(ka))) return rc2;
-                fwq_update_kernel<true, 9, 2><<<T, 512, 0, cs>>>(d, ld, d + (size_t)ka * ld, ka, T, 0,
-                                                               R0, nullptr, 0, -1);
-                if ((rc2 = closep(ka + KB))) return rc2;
-                fwq_update_kernel<true, 9, 4><<<T, 512, 0, cs>>>(d, ld, d + (size_t)ka * ld, ka, T, 0,
-                                                               R0 + 1, nullptr, 0, -1);
-                if ((rc2 = closep(ka + 2 * KB))) return rc2;
-                fwq_update_kernel<true, 9, 2><<<T, 512, 0, cs>>>(
-                    d, ld, d + (size_t)(ka + 2 * KB) * ld, ka + 2 * KB, T, 0, R0 + 1, nullptr, 0, -1);
-                if ((rc2 = closep(ka + 3 * KB))) return rc2;
-                SRT_HIPCHK(hipGetLastError());
-                SRT_HIPCHK(hipEventRecord(sc->ready[j & 1], cs));
-                return SRT_OK;
-            };
-            const int R = T / 2;
-            if ((rc = produce4(0))) return rc;
-            for (int j = 0; j < R; ++j) {
-                const int ka = 4 * j * KB;
-                u16* Pa = d + (size_t)ka * ld;
-                const bool next = j + 1 < R;
-                for (int p = 0; p < 2; p++) {
-                    SRT_HIPCHK(hipStreamWaitEvent(ss[p], sc->ready[j & 1], 0));
-                    if (next) {
-                        fwq_update_kernel<true, 13, 8><<<2 * T, 512, 0, ss[p]>>>(
-                            d, ld, Pa, ka, T, p, 2 * j + 2, nullptr, 0, -1);
-                        SRT_HIPCHK(hipEventRecord(sc->e_set[j & 1][p], ss[p]));
-                    }
-                }
-                if (next) {
-                    SRT_HIPCHK(hipStreamWaitEvent(cs, sc->e_set[j & 1][0], 0));
-                    SRT_HIPCHK(hipStreamWaitEvent(cs, sc->e_set[j & 1][1], 0));
-                    if ((rc = produce4(j + 1))) return rc;
-                }
-                const int e0 = evp ? evp->used : 0;
-                if (evp && next) {
-                    evp->group = 4;
-                    evp->used += 4;
-                }
-                for (int p = 0; p < 2; p++) {
-                    if (evp && next) SRT_HIPCHK(hipEventRecord(evp->ev[e0 + p], ss[p]));
-                    if (next)
-                        fwq_update_kernel<true, 4, 8><<<(unsigned)nset[p], 512, 0, ss[p]>>>(
-                            d, ld, Pa, ka, T, 0, 2 * j + 2, tls[p], T, 2 * j);
-                    else
-                        fwq_update_kernel<true, 5, 8><<<(unsigned)nset[p], 512, 0, ss[p]>>>(
-                            d, ld, Pa, ka, T, 0, -1, tls[p], T, 2 * j);
-                    if (evp && next) SRT_HIPCHK(hipEventRecord(evp->ev[e0 + 2 + p], ss[p]));
-                }
-                SRT_HIPCHK(hipGetLastError());
-            }
-        } else if (r128) {
-            /* 128-pivot rounds (pivot blocks a = 2j, b = 2j + 1: tile row j): every C tile stays
-             * resident for both panels (four 32-pivot stages), which halves the per-pivot C loads,
-             * row sums and stores and the bulk launches. Chain stream cs, per round j:
-             * close P_a, apply it to the cross of tile j (its row and column, XM 9), close P_b ->
-             * ready[j]. Update stream p, per round j: (after ready[j]) the cross of tile j + 1
-             * with P_a and P_b, then the rest with both, where the cross of j takes P_b only (it
-             * has P_a). The cross of j + 1 is excluded from round j's rest and updated first, so
-             * cs can close P_a' of round j + 1 under the rest; cs's cross updates touch no tile
-             * of the rest launch still running (round j - 1 excludes the cross of j). */
-            auto produce2 = [&](int j) -> int {
-                const int ka = 2 * j * KB;
-                u16* Pa = d + (size_t)ka * ld;
-                fw16_diag_kernel<true><<<1, 256, 0, cs>>>(Pa, ld, ka);
-                fw16_panel_kernel<true, true><<<2 * nb, 256, 0, cs>>>(d, ld, 0, nb, Pa, ka, nb, 1, 1);
-                if (ka > 0) fw16_refresh_kernel<<<ka / KB, 256, 0, cs>>>(d, ld, ka);
-                fwq_update_kernel<true, 9, 2><<<T, 512, 0, cs>>>(d, ld, Pa, ka, T, 0, j, nullptr, 0, -1);
-                const int kb = ka + KB;
-                u16* Pb = d + (size_t)kb * ld;
-                fw16_diag_kernel<true><<<1, 256, 0, cs>>>(Pb, ld, kb);
-                fw16_panel_kernel<true, true><<<2 * nb, 256, 0, cs>>>(d, ld, 0, nb, Pb, kb, nb, 1, 1);
-                fw16_refresh_kernel<<<kb / KB, 256, 0, cs>>>(d, ld, kb);
-                SRT_HIPCHK(hipGetLastError());
-                SRT_HIPCHK(hipEventRecord(sc->ready[j & 1], cs));
-                return SRT_OK;
-            };
-            if ((rc = produce2(0))) return rc;
-            for (int j = 0; j < T; ++j) {
-                const int ka = 2 * j * KB;
-                u16* Pa = d + (size_t)ka * ld;
-                const bool next = j + 1 < T;
-                for (int p = 0; p < 2; p++) {
-                    SRT_HIPCHK(hipStreamWaitEvent(ss[p], sc->ready[j & 1], 0));
-                    if (next) {
-                        fwq_update_kernel<true, 6, 4><<<T, 512, 0, ss[p]>>>(d, ld, Pa, ka, T, p, j + 1,
-                                                                          nullptr, 0, -1);
-                        SRT_HIPCHK(hipEventRecord(sc->e_set[j & 1][p], ss[p]));
-                    }
-                }
-                if (next) {
-                    SRT_HIPCHK(hipStreamWaitEvent(cs, sc->e_set[j & 1][0], 0));
-                    SRT_HIPCHK(hipStreamWaitEvent(cs, sc->e_set[j & 1][1], 0));
-                    if ((rc = produce2(j + 1))) return rc;
-                }
-                const int e0 = evp ? evp->used : 0;
-                if (evp && next) {
-                    evp->group = 4;
-                    evp->used += 4;
-                }
-                for (int p = 0; p < 2; p++) {
-                    if (evp && next) SRT_HIPCHK(hipEventRecord(evp->ev[e0 + p], ss[p]));
-                    if (next)
-                        fwq_update_kernel<true, 4, 4><<<(unsigned)nset[p], 512, 0, ss[p]>>>(
-                            d, ld, Pa, ka, T, 0, j + 1, tls[p], T, j);
-                    else
-                        fwq_update_kernel<true, 5, 4><<<(unsigned)nset[p], 512, 0, ss[p]>>>(
-                            d, ld, Pa, ka, T, 0, -1, tls[p], T, j);
-                    if (evp && next) SRT_HIPCHK(hipEventRecord(evp->ev[e0 + 2 + p], ss[p]));
-                }
-                SRT_HIPCHK(hipGetLastError());
-            }
-        } else {
-        if ((rc = produce(0))) return rc;
-        for (int k = 0; k < nb; ++k) {
-            const int k0 = k * KB;
-            u16* P = d + (size_t)k0 * ld;
-            const bool next = k + 1 < nb;
-            const int K1 = next ? ((k + 1) * KB) / 128 : -1;
-            for (int p = 0; p < 2; p++) {
-                SRT_HIPCHK(hipStreamWaitEvent(ss[p], sc->ready[k & 1], 0));
-                if (next) {
-                    FW_UPDATE(true, 6, T, ss[p], d, ld, P, k0, T, p, K1, nullptr, 0);
-                    SRT_HIPCHK(hipEventRecord(sc->e_set[k & 1][p], ss[p]));
-                }
-            }
-            if (next) {
-                SRT_HIPCHK(hipStreamWaitEvent(cs, sc->e_set[k & 1][0], 0));
-                SRT_HIPCHK(hipStreamWaitEvent(cs, sc->e_set[k & 1][1], 0));
-                if ((rc = produce(k + 1))) return rc;
-            }
-            /* timed as one unit: the two rest-of-round launches, from the first start to the
-             * last end (evpool group 4: start A, start B, end A, end B) */
-            const int e0 = evp ? evp->used : 0;
-            if (evp && next) {
-                evp->group = 4;
-                evp->used += 4;
-            }
-            for (int p = 0; p < 2; p++) {
-                if (evp && next) SRT_HIPCHK(hipEventRecord(evp->ev[e0 + p], ss[p]));
-                if (next)
-                    FW_UPDATE(true, 4, (unsigned)nset[p], ss[p],
-                        d, ld, P, k0, T, 0, K1, tls[p], T);
-                else
-                    FW_UPDATE(true, 5, (unsigned)nset[p], ss[p],
-                        d, ld, P, k0, T, 0, -1, tls[p], T);
-                if (evp && next) SRT_HIPCHK(hipEventRecord(evp->ev[e0 + 2 + p], ss[p]));
-            }
-            SRT_HIPCHK(hipGetLastError());
-        }
-        }
-        SRT_HIPCHK(hipEventRecord(sc->row_done, xs));
+        SRT_HIPCHK(hipStreamWaitEvent(sc->cs, sc->init_done, 0));
+        SRT_HIPCHK(hipStreamWaitEvent(sc->xs, sc->init_done, 0));
+        rc = rp == 256 ? sym_rounds<256>(sc, d, ld, st, evp, tls, nset)
+                       : sym_rounds<128>(sc, d, ld, st, evp, tls, nset);
+        if (rc) return rc;
+        SRT_HIPCHK(hipEventRecord(sc->row_done, sc->xs));
         SRT_HIPCHK(hipStreamWaitEvent(st, sc->row_done, 0));
     }
     fw16_mirror_kernel<<<dim3(nb, nb), 256, 0, st>>>(d, ld);
-    SRT_HIPCHK(hipMemsetAsync(flags[dev], 0, 2 * sizeof(int), st));
-    fw16_finish_kernel<<<dim3(srt_ceil_div(ld, 2048), ld), 256, 0, st>>>(n, ld, 0, d, lat, flags[dev],
-                                                                        CAP_F);
-    SRT_HIPCHK(hipGetLastError());
-    int hf[2] = {0, 0};
-    SRT_HIPCHK(hipMemcpyAsync(hf, flags[dev], 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-    SRT_HIPCHK(hipStreamSynchronize(st));
-    *exact = hf[0] ? 0 : 1;
-    fw16_small[dev] = hf[1] ? 0 : 1;
+    return fw16_finish(n, ld, 0, ld, d, lat, CAP_F, st, exact);
+}
+
+/* ---- row-sharded upper-triangle rounds ------------------------------------------------------- *
+ * Row-sharded symmetric FW (undirected graph, f16-compare path, R > 1 ranks; SURVEY §8e with the
+ * one-GPU upper-triangle saving). Rows stay in the srt_shard_rows blocks; of each tile pair
+ * (I, J) / (J, I) one rank keeps and updates one orientation (sym_kept), so every rank updates
+ * about half of its row block whatever its position. Round k (128 pivots: tile row k, the panels
+ * P_a over P_b) needs the full pivot panel P_k (128 x ld): column block J is in the kept tile
+ * (k, J) at the owner of tile row k, or is (J, k)^T at the owner of row J. Every rank stages the
+ * blocks it holds (transposing the latter) and broadcasts them, one grouped broadcast per round
+ * (4 MiB in all at C4); each rank then closes the diagonal blocks and updates the row panels
+ * itself (instead of a second collective in the chain). Every rank updates its kept tiles with
+ * A = P^T (column block I) and B = P (column block J), as on one GPU, on two update streams (st:
+ * even J, xs: odd J; each depends on its own launches and the panel, so their rounds overlap).
+ * After the last round each rank receives the transposes of the tiles it does not keep
+ * (point-to-point) and fills them in locally.
+ * (A 256-pivot form measured slower at N = 8: 57.6 vs 45.9 ms for one rank; 64-pivot
+ * rounds slower still.) */
+static constexpr size_t SYM_BLK = (size_t)KB * 128; /* one staged block: KB pivot rows x 128 columns */
+
+struct sym_build {
+    const srt_comm* comm = NULL;
+    int R = 0, me = 0, ld = 0, T = 0, row0 = 0, tb = 0, te = 0;
+    fw16_sched* sc = NULL;
+    hipStream_t st = NULL; /* update stream of the even-J tiles (sc->xs: odd J) and of the fill */
+    evpool_t* evp = NULL;
+    u16* d = NULL;     /* this rank's rows */
+    u16* pbuf[2] = {}; /* the closed panels P_k (128 x ld), by k & 1 */
+    /* plan: tile-row range of every rank, owner of each tile row, this rank's kept tiles (even J
+     * first, then odd J: the lists of the two update streams), blocks per contributor of a band */
+    std::vector<int> qtb, qte, own, cnt;
+    std::vector<uint32_t> kept;
+    size_t nset[2] = {0, 0};
+    /* device scratch, freed by the destructor: kept-tile list, owner of each tile row, three
+     * staged bands in (contributor, J) order (rows a, then b), and the final fill's pair list,
+     * send and receive tiles */
+    uint32_t* tl = NULL;
+    int* down = NULL;
+    u16* grecv = NULL;
+    uint32_t* dp = NULL;
+    u16 *fsend = NULL, *frecv = NULL;
+
+    u16* sa_of(int j) const { return grecv + (size_t)(j % 3) * 2 * ((size_t)T + 1) * SYM_BLK; }
+    u16* sb_of(int j) const { return sa_of(j) + ((size_t)T + 1) * SYM_BLK; }
+    /* every exit: the three streams drain before the scratch they use goes */
+    ~sym_build() {
+        (void)hipStreamSynchronize(sc->cs);
+        (void)hipStreamSynchronize(sc->ms);
+        (void)hipStreamSynchronize(st);
+        if (tl) (void)hipFree(tl);
+        if (down) (void)hipFree(down);
+        if (grecv) (void)hipFree(grecv);
+        if (dp) (void)hipFree(dp);
+        if (fsend) (void)hipFree(fsend);
+        if (frecv) (void)hipFree(frecv);
+    }
+};
+
+/* tile-row ranges of every rank, the owner of each tile row, this rank's kept tiles; the device
+ * scratch of the rounds */
+static int sym_plan(sym_build& b) {
+    const int R = b.R, T = b.T;
+    b.qtb.resize(R);
+    b.qte.resize(R);
+    b.own.assign(T, 0);
+    b.cnt.assign(R, 0);
+    for (int q = 0; q < R; q++) {
+        int32_t qb, qe;
+        srt_shard_rows(b.ld, SRT_SHARD_ALIGN, R, q, &qb, &qe);
+        b.qtb[q] = qb / 128;
+        b.qte[q] = qe / 128;
+        for (int K = b.qtb[q]; K < b.qte[q] && K < T; K++) b.own[K] = q;
+    }
+    /* kept tiles, even J first, then odd J: the lists of the two update streams */
+    for (int p = 0; p < 2; p++)
+        for (int I = b.tb; I < b.te; I++)
+            for (int J = p; J < T; J += 2)
+                if (sym_kept(I, J)) {
+                    b.kept.push_back(((uint32_t)I << 16) | (uint32_t)J);
+                    b.nset[p]++;
+                }
+    /* band k + 3 is staged while bands k + 1 and k + 2 wait for their panels: three bands */
+    const size_t nstage = 2 * ((size_t)T + 1) * SYM_BLK * 3;
+    SRT_HIPCHK(hipMalloc(&b.tl, (b.kept.size() + 1) * sizeof(uint32_t)));
+    SRT_HIPCHK(hipMalloc(&b.down, (size_t)T * sizeof(int)));
+    SRT_HIPCHK(hipMalloc(&b.grecv, nstage * sizeof(u16)));
+    SRT_HIPCHK(hipMemcpyAsync(b.down, b.own.data(), (size_t)T * sizeof(int), hipMemcpyHostToDevice, b.st));
+    SRT_HIPCHK(hipStreamSynchronize(b.st));
+    /* timing-only communicator: the blocks other ranks would send stay a small constant, so the
+     * arithmetic keeps the u16 tier and the u8 post pass (the tables are not correct) */
+    if (srt_comm_is_solo(b.comm)) SRT_HIPCHK(hipMemsetD16Async((hipDeviceptr_t)b.grecv, 3, nstage, b.st));
+    if (!b.kept.empty()) { /* pageable source: finished before the host list can change */
+        SRT_HIPCHK(hipMemcpyAsync(b.tl, b.kept.data(), b.kept.size() * sizeof(uint32_t),
+                                  hipMemcpyHostToDevice, b.st));
+        SRT_HIPCHK(hipStreamSynchronize(b.st));
+    }
     return SRT_OK;
 }
 
-/* Row-sharded symmetric FW (undirected graph, f16-compare path, R > 1 ranks; SURVEY §8e with the
- * one-GPU upper-triangle saving). Rows stay in the srt_shard_rows blocks; of each tile pair
- * (I, J) / (J, I) one rank keeps and updates one orientation (sym_kept), so every rank updates
- * about half of its row block whatever its position. Round k needs the full pivot panel P_k (64 x
- * ld): column block J is in the kept tile (K, J) at the owner of tile row K, or is (J, K)^T at
- * the owner of row J. Every rank stages the blocks it holds (transposing the latter) and
- * broadcasts them, one grouped broadcast per round (4 MiB in all at C4); each rank then closes
- * the diagonal block and updates the row panel itself (24 us, instead of a second collective
- * in the chain), and the owner writes the result back into its pivot rows. Every rank updates
- * its kept tiles with A = P^T (column block I) and B = P (column block J), as on one GPU.
- * Lookahead as in srt_fw16_build: each round first updates the kept tiles of the next pivot
- * block's tile row and column (XM 3), the high-priority stream cs assembles and closes the next
- * panel under the rest of the round (XM 4). After the last round each rank receives the
- * transposes of the tiles it does not keep (point-to-point) and fills them in locally. */
-static int fw16_build_sym_sharded(const srt_comm* comm, int n, int ld, int row0, int nrows,
-                                  const uint32_t* w_rows, uint32_t* lat_rows, hipStream_t st,
-                                  evpool_t* evp, int* exact, int kbr) {
-    const int dev = srt_state_slot();
-    const int R = srt_comm_size(comm), me = srt_comm_rank(comm);
-    /* kbr = 128: 128-pivot rounds (pivot block = tile row K, panels P_a over P_b, four 32-pivot
-     * stages per C-tile residency); kbr = 64: 64-pivot rounds */
-    const bool r128 = kbr == 128;
-    const int T = ld / 128, nb = ld / kbr;
-    const int tb = row0 / 128, te = (row0 + nrows) / 128;
-    size_t* caps = fw16_caps;
-    int** flags = fw16_flags;
-    const size_t need = (size_t)nrows * ld + 2 * (size_t)kbr * ld;
-    if (caps[dev] < need || !fw16_bufs[dev]) {
-        if (fw16_bufs[dev]) SRT_HIPCHK(hipFree(fw16_bufs[dev]));
-        fw16_bufs[dev] = NULL;
-        caps[dev] = 0;
-        SRT_HIPCHK(hipMalloc(&fw16_bufs[dev], need * sizeof(u16)));
-        caps[dev] = need;
+/* on the band stream ms: pack band j (tile row j: the blocks this rank holds, both halves in one
+ * launch), broadcast every contributor's blocks as two half-panels, mark the band's arrival */
+static int sym_send(sym_build& b, int j) {
+    hipStream_t ms = b.sc->ms;
+    const int T = b.T;
+    u16* sa = b.sa_of(j);
+    u16* sb = b.sb_of(j);
+    /* column block J comes from the keeper of (j, J): the owner of row j, or of row J */
+    std::fill(b.cnt.begin(), b.cnt.end(), 0);
+    for (int J = 0; J < T; J++) b.cnt[sym_kept(j, J) ? b.own[j] : b.own[J]]++;
+    if (b.cnt[b.me])
+        sym_contrib_pack_kernel<<<2 * T, 256, 0, ms>>>(b.d, b.ld, b.row0, b.tb, j, j * 128, T, b.down,
+                                                       b.me, sa, sb);
+    SRT_HIPCHK(hipGetLastError());
+    int r = srt_coll_group_begin(b.comm);
+    size_t off = 0;
+    for (int q = 0; q < b.R && !r; q++) {
+        if (b.cnt[q]) {
+            const size_t bytes = (size_t)b.cnt[q] * SYM_BLK * sizeof(u16);
+            r = srt_coll_bcast(b.comm, sa + off * SYM_BLK, bytes, q, ms);
+            if (!r) r = srt_coll_bcast(b.comm, sb + off * SYM_BLK, bytes, q, ms);
+        }
+        off += (size_t)b.cnt[q];
     }
-    if (!flags[dev]) SRT_HIPCHK(hipMalloc(&flags[dev], 2 * sizeof(int)));
-    fw16_sched* sc;
-    int rc = sched_get(&sc, dev);
-    if (rc) return rc;
-    hipStream_t cs = sc->cs;
-    u16* d = fw16_bufs[dev];
-    u16* pbuf[2] = {d + (size_t)nrows * ld, d + (size_t)nrows * ld + (size_t)kbr * ld};
-    /* tile-row ranges of every rank, the owner of each tile row, this rank's kept tiles */
-    int* qtb = (int*)malloc((size_t)R * sizeof(int));
-    int* qte = (int*)malloc((size_t)R * sizeof(int));
-    int* own = (int*)malloc((size_t)T * sizeof(int));
-    const size_t maxkept = (size_t)(te - tb) * T + 1;
-    uint32_t* hkept = (uint32_t*)malloc(maxkept * sizeof(uint32_t));
-    if (!qtb || !qte || !own || !hkept) {
-        free(qtb);
-        free(qte);
-        free(own);
-        free(hkept);
-        return SRT_E_NOMEM;
+    const int r2 = srt_coll_group_end(b.comm);
+    if (r || r2) return r ? r : r2;
+    SRT_HIPCHK(hipEventRecord(b.sc->arr[j % 3], ms));
+    return SRT_OK;
+}
+
+/* on cs: the staged band j (complete) -> P_j. Every rank closes P_a, applies it to the staged b
+ * rows (sym_cross_stage_kernel), then closes P_b -- P = P_a over P_b, 128 x ld */
+static int sym_close(sym_build& b, int j) {
+    hipStream_t cs = b.sc->cs;
+    const int T = b.T, ld = b.ld, j0 = j * 128;
+    u16* P = b.pbuf[j & 1];
+    u16* Pb = P + (size_t)KB * ld;
+    u16* sa = b.sa_of(j);
+    u16* sb = b.sb_of(j);
+    sym_diag_stage_kernel<<<1, 256, 0, cs>>>(P, ld, j, j0, T, b.down, sa, nullptr);
+    sym_panel_stage_kernel<SYM_RM><<<T, 1024 / SYM_RM, 0, cs>>>(P, ld, j, j0, T, b.down, sa, nullptr);
+    sym_cross_stage_kernel<SYM_RM><<<T, 1024 / SYM_RM, 0, cs>>>(P, ld, j, T, b.down, sb, j, 0);
+    sym_diag_stage_kernel<<<1, 256, 0, cs>>>(Pb, ld, j, j0 + KB, T, b.down, sb, nullptr);
+    sym_panel_stage_kernel<SYM_RM><<<T, 1024 / SYM_RM, 0, cs>>>(Pb, ld, j, j0 + KB, T, b.down, sb, nullptr);
+    SRT_HIPCHK(hipGetLastError());
+    SRT_HIPCHK(hipEventRecord(b.sc->ready[j & 1], cs));
+    return SRT_OK;
+}
+
+/* P_k into the staged band j: the band's last panel (j = k + 1) on cs, on the chain from
+ * P_k to P_{k+1}; its first (j = k + 2) on the band stream ms, which has broadcast the
+ * band and then idles until round k's update ends (its next send): off the chain, and
+ * no fifth stream (four hardware queues per process: a fifth would share one, and a
+ * wait there stalls an update stream). The last apply of band j waits for it
+ * (applied[j]). */
+static int sym_apply(sym_build& b, int k, int j) {
+    fw16_sched* sc = b.sc;
+    hipStream_t as = j == k + 1 ? sc->cs : sc->ms;
+    if (j == k + 1) {
+        SRT_HIPCHK(hipStreamWaitEvent(sc->cs, sc->arr[j % 3], 0));
+        if (j >= 2) SRT_HIPCHK(hipStreamWaitEvent(sc->cs, sc->applied[j % 3], 0));
+    } else {
+        SRT_HIPCHK(hipStreamWaitEvent(sc->ms, sc->ready[k & 1], 0));
     }
+    fwq_band_kernel<<<b.T, 512, 0, as>>>(b.pbuf[k & 1], b.ld, j, b.T, b.down, b.sa_of(j), b.sb_of(j));
+    SRT_HIPCHK(hipGetLastError());
+    if (j == k + 2) SRT_HIPCHK(hipEventRecord(sc->applied[j % 3], sc->ms));
+    return SRT_OK;
+}
+
+/* Two-deep rounds. Band j (tile row j, rows a then b) is packed from the real tiles
+ * after round j - 3's update (panels <= j - 3; the update of round j - 2 may already
+ * be writing them -- every value read is a real path length no larger than what the
+ * round needs, as with the two update streams), broadcast on the band stream ms, and
+ * takes P_{j-2} and P_{j-1} on arrival (fwq_band_kernel) before it is closed
+ * into P_j. The broadcast then has a whole round of the update to hide under, and the
+ * chain from P_k to P_{k+1} is one band apply plus the closures. The update launches
+ * cover every kept tile (no cross exclusions): the pivot rows take their own closed
+ * panel there (min-plus with a closed panel is idempotent), so the closures write no
+ * pivot rows. With one or two tile rows the prologue sends every band there is and the
+ * loop sends none. */
+static int sym_rounds_sharded(sym_build& b) {
+    fw16_sched* sc = b.sc;
+    evpool_t* evp = b.evp;
+    hipStream_t cs = sc->cs, ms = sc->ms, ss[2] = {b.st, sc->xs};
+    const uint32_t* tls[2] = {b.tl, b.tl + b.nset[0]};
+    const int nb = b.T;
+    int rc;
+    SRT_HIPCHK(hipStreamWaitEvent(ms, sc->init_done, 0));
+    for (int j = 0; j < 3 && j < nb; j++)
+        if ((rc = sym_send(b, j))) return rc;
+    SRT_HIPCHK(hipStreamWaitEvent(cs, sc->arr[0], 0));
+    if ((rc = sym_close(b, 0))) return rc;
+    int timed = 0; /* rounds timed as one unit: the first start and the last end (evpool) */
+    for (int k = 0; k < nb; ++k) {
+        const bool next = k + 1 < nb;
+        /* the unit's period only needs the first round's starts and the last round's ends
+         * (evpool_sum, group 4): two records per round fewer on the host's critical path */
+        const bool t_first = evp && next && timed == 0, t_last = evp && k + 2 == nb;
+        if (evp && next) {
+            evp->group = 4;
+            evp->used = 4 * ++timed;
+        }
+        for (int p = 0; p < 2; p++) {
+            SRT_HIPCHK(hipStreamWaitEvent(ss[p], sc->ready[k & 1], 0));
+            if (t_first) SRT_HIPCHK(hipEventRecord(evp->ev[p], ss[p]));
+            if (b.nset[p])
+                fwq_update_kernel<true, 5, 4><<<(unsigned)b.nset[p], 512, 0, ss[p]>>>(
+                    b.d, b.ld, b.pbuf[k & 1], k * 128, b.T, b.tb, -1, tls[p], b.te);
+            if (t_last) SRT_HIPCHK(hipEventRecord(evp->ev[evp->used - 2 + p], ss[p]));
+            SRT_HIPCHK(hipEventRecord(sc->e_set[k & 1][p], ss[p]));
+        }
+        SRT_HIPCHK(hipGetLastError());
+        /* band stream: P_k into band k + 2 (arrived), then band k + 3 once round k's
+         * update has (at least) passed over its tiles */
+        if (k + 2 < nb && (rc = sym_apply(b, k, k + 2))) return rc;
+        if (k + 3 < nb) {
+            SRT_HIPCHK(hipStreamWaitEvent(ms, sc->e_set[k & 1][0], 0));
+            SRT_HIPCHK(hipStreamWaitEvent(ms, sc->e_set[k & 1][1], 0));
+            if ((rc = sym_send(b, k + 3))) return rc;
+        }
+        if (!next) continue;
+        if ((rc = sym_apply(b, k, k + 1))) return rc;
+        if (k >= 1) { /* P_{k+1} overwrites P_{k-1}: its update launches are done */
+            SRT_HIPCHK(hipStreamWaitEvent(cs, sc->e_set[(k - 1) & 1][0], 0));
+            SRT_HIPCHK(hipStreamWaitEvent(cs, sc->e_set[(k - 1) & 1][1], 0));
+        }
+        if ((rc = sym_close(b, k + 1))) return rc;
+    }
+    return SRT_OK;
+}
+
+/* fill the tiles this rank does not keep: transposes from their keepers */
+static int sym_fill(sym_build& b) {
+    const int R = b.R, me = b.me, tb = b.tb, te = b.te, ld = b.ld;
+    const std::vector<int>& qtb = b.qtb;
+    const std::vector<int>& qte = b.qte;
+    hipStream_t st = b.st;
+    u16* d = b.d;
+    auto pair = [](int I, int J) { return ((uint32_t)I << 16) | (uint32_t)J; };
+    size_t nloc = 0, stot = 0, rtot = 0;
+    std::vector<size_t> scount(R, 0), rcount(R, 0);
     for (int q = 0; q < R; q++) {
-        int32_t qb, qe;
-        srt_shard_rows(ld, SRT_SHARD_ALIGN, R, q, &qb, &qe);
-        qtb[q] = qb / 128;
-        qte[q] = qe / 128;
-        for (int K = qtb[q]; K < qte[q] && K < T; K++) own[K] = q;
+        for (int I = tb; I < te; I++) /* this rank keeps (I, J), J in q's rows */
+            for (int J = qtb[q]; J < qte[q]; J++)
+                if (I != J && sym_kept(I, J)) (q == me ? nloc : scount[q])++;
+        if (q != me)
+            for (int I = qtb[q]; I < qte[q]; I++) /* q keeps (I, J), J in this rank's rows */
+                for (int J = tb; J < te; J++)
+                    if (sym_kept(I, J)) rcount[q]++;
+        stot += scount[q];
+        rtot += rcount[q];
     }
-    /* kept tiles, even J first, then odd J: the lists of the two update streams */
-    size_t nkept = 0, nset[2] = {0, 0};
-    for (int p = 0; p < 2; p++)
-        for (int I = tb; I < te; I++)
-            for (int J = p; J < T; J += 2)
-                if (sym_kept(I, J)) {
-                    hkept[nkept++] = ((uint32_t)I << 16) | (uint32_t)J;
-                    nset[p]++;
-                }
-    /* device scratch: kept-tile list, gather send (this rank's rows) and receive (a panel) */
-    uint32_t* tl = NULL;
-    int* down = NULL; /* owner of each tile row, on the device */
-    u16* grecv = NULL; /* staged panel blocks in (contributor, J) order (r128: rows a, then b) */
-    int* cnt = (int*)calloc(2 * (size_t)R, sizeof(int)); /* per contributor (256: two tile rows) */
-    const size_t blk = (size_t)KB * 128;
-    /* two-deep 128-pivot rounds (N > 1 with two or more tile rows): band k + 3 is staged
-     * and broadcast on its own stream right after round k's update, three rounds ahead, and each
-     * rank applies the two panels it missed to the staged band itself (fwq_band_kernel) */
-    const bool deep = r128 && R > 1 && T >= 2;
-    const size_t nstage = (size_t)(kbr / KB) * ((size_t)T + 1) * blk * (deep ? 3 : 1);
-    bool ok = cnt && hipMalloc(&tl, (nkept + 1) * sizeof(uint32_t)) == hipSuccess &&
-              hipMalloc(&down, (size_t)T * sizeof(int)) == hipSuccess &&
-              hipMalloc(&grecv, nstage * sizeof(u16)) == hipSuccess;
-    if (ok)
-        ok = hipMemcpyAsync(down, own, (size_t)T * sizeof(int), hipMemcpyHostToDevice, st) ==
-                 hipSuccess &&
-             hipStreamSynchronize(st) == hipSuccess;
-    /* timing-only communicator: the blocks other ranks would send stay a small constant, so the
-     * arithmetic keeps the u16 tier and the u8 post pass (the tables are not correct) */
-    if (ok && srt_comm_is_solo(comm))
-        ok = hipMemsetD16Async((hipDeviceptr_t)grecv, 3, nstage, st) == hipSuccess;
-    void** sp = (void**)calloc((size_t)R, sizeof(void*));
-    void** rp = (void**)calloc((size_t)R, sizeof(void*));
-    size_t* sbytes = (size_t*)calloc((size_t)R, sizeof(size_t));
-    size_t* rbytes = (size_t*)calloc((size_t)R, sizeof(size_t));
-    ok = ok && sp && rp && sbytes && rbytes;
-    if (ok && nkept) /* pageable source: finished before the host list can change */
-        ok = hipMemcpyAsync(tl, hkept, nkept * sizeof(uint32_t), hipMemcpyHostToDevice, st) ==
-                 hipSuccess &&
-             hipStreamSynchronize(st) == hipSuccess;
-#define SYM_FAIL(code)                                                                             \
-    do {                                                                                           \
-        rc = (code);                                                                               \
-        goto out;                                                                                  \
-    } while (0)
-#define SYM_HIP(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            srt_set_error("HIP error %s at %s:%d (%s)", hipGetErrorString(e_), __FILE__,           \
-                          __LINE__, #expr);                                                        \
-            SYM_FAIL(SRT_E_DEVICE);                                                                \
-        }                                                                                          \
-    } while (0)
-    {
-        if (!ok) {
-            srt_set_error("sharded symmetric FW: scratch allocation failed");
-            SYM_FAIL(SRT_E_NOMEM);
-        }
-        if (nrows > 0)
-            fw16_init_kernel<<<dim3(srt_ceil_div(ld, 2048), nrows), 256, 0, st>>>(n, ld, row0, w_rows,
-                                                                               d, CAP_F);
-        SYM_HIP(hipGetLastError());
-        SYM_HIP(hipEventRecord(sc->init_done, st));
-        SYM_HIP(hipStreamWaitEvent(cs, sc->init_done, 0));
-        auto panel_of = [&](int k) -> u16* { return pbuf[k & 1]; };
-        /* on cs: assemble P_k from every rank's blocks (its tiles' round k-1 values are final),
-         * then every rank closes the diagonal block and updates the row panel itself; the owner
-         * also writes the result back into its pivot rows */
-        auto produce = [&](int k) -> int {
-            const int k0 = k * KB, K = k0 / 128, o = own[K];
-            /* P was last read by round k-2's rest launches, which precede round k-1's next-row
-             * launches on both update streams; cs waited for those (e_set), so it is free */
-            u16* P = pbuf[k & 1];
-            for (int q = 0; q < R; q++) cnt[q] = 0;
-            for (int J = 0; J < T; J++) cnt[sym_kept(K, J) ? o : own[J]]++;
-            if (cnt[me])
-                sym_contrib_pack_kernel<<<T, 256, 0, cs>>>(d, ld, row0, tb, K, k0, T, down, me, grecv);
-            SRT_HIPCHK(hipGetLastError());
-            int r = srt_coll_group_begin(comm);
-            size_t off = 0;
-            for (int q = 0; q < R && !r; q++) {
-                if (cnt[q])
-                    r = srt_coll_bcast(comm, grecv + off * blk, (size_t)cnt[q] * blk * sizeof(u16), q, cs);
-                off += (size_t)cnt[q];
-            }
-            const int r2 = srt_coll_group_end(comm);
-            if (r || r2) return r ? r : r2;
-            /* straight from the staged blocks: closure, then row panel (+ the owner's rows) */
-            u16* prow = me == o ? d + (size_t)(k0 - row0) * ld : nullptr;
-            sym_diag_stage_kernel<<<1, 256, 0, cs>>>(P, ld, K, k0, T, down, grecv, prow);
-            sym_panel_stage_kernel<SYM_RM><<<T, 1024 / SYM_RM, 0, cs>>>(P, ld, K, k0, T, down, grecv, prow);
-            SRT_HIPCHK(hipGetLastError());
-            SRT_HIPCHK(hipEventRecord(sc->ready[k & 1], cs));
-            return SRT_OK;
-        };
-        /* 128-pivot rounds: the band of tile row K (rows a, then b) is staged and broadcast as
-         * two half-panels; every rank closes P_a, applies it to the staged b rows
-         * (sym_cross_stage_kernel), then closes P_b -- P = P_a over P_b, 128 x ld */
-        auto produce128 = [&](int k) -> int {
-            const int k0 = k * 128, K = k, o = own[K];
-            u16* P = pbuf[k & 1];
-            u16* sa = grecv;
-            u16* sb = grecv + ((size_t)T + 1) * blk;
-            for (int q = 0; q < R; q++) cnt[q] = 0;
-            for (int J = 0; J < T; J++) cnt[sym_kept(K, J) ? o : own[J]]++;
-            if (cnt[me]) /* both halves in one launch */
-                sym_contrib_pack_kernel<<<2 * T, 256, 0, cs>>>(d, ld, row0, tb, K, k0, T, down, me, sa,
-                                                               sb);
-            SRT_HIPCHK(hipGetLastError());
-            int r = srt_coll_group_begin(comm);
-            size_t off = 0;
-            for (int q = 0; q < R && !r; q++) {
-                if (cnt[q]) {
-                    const size_t bytes = (size_t)cnt[q] * blk * sizeof(u16);
-                    r = srt_coll_bcast(comm, sa + off * blk, bytes, q, cs);
-                    if (!r) r = srt_coll_bcast(comm, sb + off * blk, bytes, q, cs);
-                }
-                off += (size_t)cnt[q];
-            }
-            const int r2 = srt_coll_group_end(comm);
-            if (r || r2) return r ? r : r2;
-            u16* prow_a = me == o ? d + (size_t)(k0 - row0) * ld : nullptr;
-            u16* prow_b = prow_a ? prow_a + (size_t)KB * ld : nullptr;
-            u16* Pb = P + (size_t)KB * ld;
-            sym_diag_stage_kernel<<<1, 256, 0, cs>>>(P, ld, K, k0, T, down, sa, prow_a);
-            sym_panel_stage_kernel<SYM_RM><<<T, 1024 / SYM_RM, 0, cs>>>(P, ld, K, k0, T, down, sa, prow_a);
-            sym_cross_stage_kernel<SYM_RM><<<T, 1024 / SYM_RM, 0, cs>>>(P, ld, K, T, down, sb, K, 0);
-            sym_diag_stage_kernel<<<1, 256, 0, cs>>>(Pb, ld, K, k0 + KB, T, down, sb, prow_b);
-            sym_panel_stage_kernel<SYM_RM><<<T, 1024 / SYM_RM, 0, cs>>>(Pb, ld, K, k0 + KB, T, down, sb, prow_b);
-            SRT_HIPCHK(hipGetLastError());
-            SRT_HIPCHK(hipEventRecord(sc->ready[k & 1], cs));
-            return SRT_OK;
-        };
-        auto make = [&](int k) -> int { return r128 ? produce128(k) : produce(k); };
-        /* two update streams (st: even J, xs: odd J), as on one GPU (fw16_build_sym): each
-         * depends on its own launches and the panel, so their rounds overlap */
-        hipStream_t ss[2] = {st, sc->xs};
-        const uint32_t* tls[2] = {tl, tl + nset[0]};
-        SYM_HIP(hipStreamWaitEvent(sc->xs, sc->init_done, 0));
-        if (deep) {
-            /* Two-deep rounds. Band j (tile row j, rows a then b) is packed from the real tiles
-             * after round j - 3's update (panels <= j - 3; the update of round j - 2 may already
-             * be writing them -- every value read is a real path length no larger than what the
-             * round needs, as with the two update streams), broadcast on the band stream ms, and
-             * takes P_{j-2} and P_{j-1} on arrival (fwq_band_kernel, on cs) before it is closed
-             * into P_j. The broadcast then has a whole round of the update to hide under, and the
-             * chain from P_k to P_{k+1} is one band apply plus the closures. The update launches
-             * cover every kept tile (no cross exclusions): the pivot rows take their own closed
-             * panel there (min-plus with a closed panel is idempotent), so the closures write no
-             * pivot rows. */
-            hipStream_t ms = sc->ms;
-            auto sa_of = [&](int j) { return grecv + (size_t)(j % 3) * 2 * ((size_t)T + 1) * blk; };
-            auto sb_of = [&](int j) { return sa_of(j) + ((size_t)T + 1) * blk; };
-            auto send = [&](int j) -> int { /* on ms: pack band j, broadcast, mark its arrival */
-                const int o = own[j];
-                u16* sa = sa_of(j);
-                u16* sb = sb_of(j);
-                for (int q = 0; q < R; q++) cnt[q] = 0;
-                for (int J = 0; J < T; J++) cnt[sym_kept(j, J) ? o : own[J]]++;
-                if (cnt[me])
-                    sym_contrib_pack_kernel<<<2 * T, 256, 0, ms>>>(d, ld, row0, tb, j, j * 128, T, down,
-                                                                   me, sa, sb);
-                SRT_HIPCHK(hipGetLastError());
-                int r = srt_coll_group_begin(comm);
-                size_t off = 0;
-                for (int q = 0; q < R && !r; q++) {
-                    if (cnt[q]) {
-                        const size_t bytes = (size_t)cnt[q] * blk * sizeof(u16);
-                        r = srt_coll_bcast(comm, sa + off * blk, bytes, q, ms);
-                        if (!r) r = srt_coll_bcast(comm, sb + off * blk, bytes, q, ms);
-                    }
-                    off += (size_t)cnt[q];
-                }
-                const int r2 = srt_coll_group_end(comm);
-                if (r || r2) return r ? r : r2;
-                SRT_HIPCHK(hipEventRecord(sc->arr[j % 3], ms));
-                return SRT_OK;
-            };
-            auto close = [&](int j) -> int { /* on cs: the staged band j (complete) -> P_j */
-                const int j0 = j * 128;
-                u16* P = pbuf[j & 1];
-                u16* Pb = P + (size_t)KB * ld;
-                u16* sa = sa_of(j);
-                u16* sb = sb_of(j);
-                sym_diag_stage_kernel<<<1, 256, 0, cs>>>(P, ld, j, j0, T, down, sa, nullptr);
-                sym_panel_stage_kernel<SYM_RM><<<T, 1024 / SYM_RM, 0, cs>>>(P, ld, j, j0, T, down, sa, nullptr);
-                sym_cross_stage_kernel<SYM_RM><<<T, 1024 / SYM_RM, 0, cs>>>(P, ld, j, T, down, sb, j, 0);
-                sym_diag_stage_kernel<<<1, 256, 0, cs>>>(Pb, ld, j, j0 + KB, T, down, sb, nullptr);
-                sym_panel_stage_kernel<SYM_RM><<<T, 1024 / SYM_RM, 0, cs>>>(Pb, ld, j, j0 + KB, T, down, sb, nullptr);
-                SRT_HIPCHK(hipGetLastError());
-                SRT_HIPCHK(hipEventRecord(sc->ready[j & 1], cs));
-                return SRT_OK;
-            };
-            /* P_k into the staged band j: the band's last panel (j = k + 1) on cs, on the chain from
-             * P_k to P_{k+1}; its first (j = k + 2) on the band stream ms, which has broadcast the
-             * band and then idles until round k's update ends (its next send): off the chain, and
-             * no fifth stream (four hardware queues per process: a fifth would share one, and a
-             * wait there stalls an update stream). The last apply of band j waits for it
-             * (applied[j]). */
-            auto apply = [&](int k, int j) -> int {
-                hipStream_t as = j == k + 1 ? cs : ms;
-                if (j == k + 1) {
-                    SRT_HIPCHK(hipStreamWaitEvent(cs, sc->arr[j % 3], 0));
-                    if (j >= 2) SRT_HIPCHK(hipStreamWaitEvent(cs, sc->applied[j % 3], 0));
-                } else {
-                    SRT_HIPCHK(hipStreamWaitEvent(ms, sc->ready[k & 1], 0));
-                }
-                fwq_band_kernel<<<T, 512, 0, as>>>(pbuf[k & 1], ld, j, T, down, sa_of(j), sb_of(j));
-                SRT_HIPCHK(hipGetLastError());
-                if (j == k + 2) SRT_HIPCHK(hipEventRecord(sc->applied[j % 3], ms));
-                return SRT_OK;
-            };
-            SYM_HIP(hipStreamWaitEvent(ms, sc->init_done, 0));
-            for (int j = 0; j < 3 && j < nb; j++)
-                if ((rc = send(j))) goto out;
-            SYM_HIP(hipStreamWaitEvent(cs, sc->arr[0], 0));
-            if ((rc = close(0))) goto out;
-            int timed = 0;
-            for (int k = 0; k < nb; ++k) {
-                u16* P = panel_of(k);
-                const bool next = k + 1 < nb;
-                const bool t_first = evp && next && timed == 0, t_last = evp && k + 2 == nb;
-                if (evp && next) {
-                    evp->group = 4;
-                    evp->used = 4 * ++timed;
-                }
-                for (int p = 0; p < 2; p++) {
-                    SYM_HIP(hipStreamWaitEvent(ss[p], sc->ready[k & 1], 0));
-                    if (t_first) SYM_HIP(hipEventRecord(evp->ev[p], ss[p]));
-                    if (nset[p])
-                        fwq_update_kernel<true, 5, 4><<<(unsigned)nset[p], 512, 0, ss[p]>>>(
-                            d, ld, P, k * 128, T, tb, -1, tls[p], te);
-                    if (t_last) SYM_HIP(hipEventRecord(evp->ev[evp->used - 2 + p], ss[p]));
-                    SYM_HIP(hipEventRecord(sc->e_set[k & 1][p], ss[p]));
-                }
-                SYM_HIP(hipGetLastError());
-                /* band stream: P_k into band k + 2 (arrived), then band k + 3 once round k's
-                 * update has (at least) passed over its tiles */
-                if (k + 2 < nb && (rc = apply(k, k + 2))) goto out;
-                if (k + 3 < nb) {
-                    SYM_HIP(hipStreamWaitEvent(ms, sc->e_set[k & 1][0], 0));
-                    SYM_HIP(hipStreamWaitEvent(ms, sc->e_set[k & 1][1], 0));
-                    if ((rc = send(k + 3))) goto out;
-                }
-                if (!next) continue;
-                if ((rc = apply(k, k + 1))) goto out;
-                if (k >= 1) { /* P_{k+1} overwrites P_{k-1}: its update launches are done */
-                    SYM_HIP(hipStreamWaitEvent(cs, sc->e_set[(k - 1) & 1][0], 0));
-                    SYM_HIP(hipStreamWaitEvent(cs, sc->e_set[(k - 1) & 1][1], 0));
-                }
-                if ((rc = close(k + 1))) goto out;
-            }
-        } else {
-        if ((rc = make(0))) goto out;
-        /* Host enqueue order per round: next-row launches, the rest launches, then the next
-         * panel on cs. At N ranks a round is ~100 us of GPU work and ~20 HIP calls, so the host
-         * is the bottleneck if the bulk update waits behind the chain's calls; the chain kernels
-         * run at raised wave priority wherever they land (FW_CHAIN_PRIO). */
-        int timed = 0; /* rounds timed as one unit: the first start and the last end (evpool) */
-        /* The next pivot row's cross runs on the chain stream (after both streams' rest of the
-         * round before, whose tiles it follows), so the update streams run their rest launches
-         * back to back instead of NR -> rest with two launch gaps a round: one rank of N = 8
-         * 49.2 -> 46.0 ms, N = 4 unchanged (83.5 ms). (retired one-GPU NRCS form) keeps NR on the update
-         * streams. */
-        for (int k = 0; k < nb; ++k) {
-            const int k0 = k * kbr;
-            u16* P = panel_of(k);
-            const bool next = k + 1 < nb;
-            const int K1 = next ? (k + 1) * kbr / 128 : -1;
-            for (int p = 0; p < 2; p++) SYM_HIP(hipStreamWaitEvent(ss[p], sc->ready[k & 1], 0));
-            /* the unit's period only needs the first round's starts and the last round's ends
-             * (evpool_sum, group 4): two records per round fewer on the host's critical path */
-            const bool t_first = evp && next && timed == 0, t_last = evp && k + 2 == nb;
-            if (evp && next) {
-                evp->group = 4;
-                evp->used = 4 * ++timed;
-            }
-            for (int p = 0; p < 2; p++) {
-                if (t_first) SYM_HIP(hipEventRecord(evp->ev[p], ss[p]));
-                if (nset[p] && r128) {
-                    if (next)
-                        fwq_update_kernel<true, 4, 4><<<(unsigned)nset[p], 512, 0, ss[p]>>>(
-                            d, ld, P, k0, T, tb, K1, tls[p], te);
-                    else
-                        fwq_update_kernel<true, 5, 4><<<(unsigned)nset[p], 512, 0, ss[p]>>>(
-                            d, ld, P, k0, T, tb, -1, tls[p], te);
-                } else if (nset[p]) {
-                    if (next)
-                        FW_UPDATE(true, 4, (unsigned)nset[p], ss[p],
-                            d, ld, P, k0, T, tb, K1, tls[p], te);
-                    else
-                        FW_UPDATE(true, 5, (unsigned)nset[p], ss[p],
-                            d, ld, P, k0, T, tb, -1, tls[p], te);
-                }
-                if (t_last) SYM_HIP(hipEventRecord(evp->ev[evp->used - 2 + p], ss[p]));
-            }
-            SYM_HIP(hipGetLastError());
-            /* rest(k) done: round k + 1's cross follows it on the chain stream */
-            for (int p = 0; p < 2; p++) SYM_HIP(hipEventRecord(sc->e_set[k & 1][p], ss[p]));
-            if (next) {
-                /* the cross of K1 was last updated by rest(k - 1); P of round k + 1's buffer was
-                 * last read by rest(k - 1) and the cross of round k - 1 (on cs) */
-                if (k >= 1) {
-                    SYM_HIP(hipStreamWaitEvent(cs, sc->e_set[(k - 1) & 1][0], 0));
-                    SYM_HIP(hipStreamWaitEvent(cs, sc->e_set[(k - 1) & 1][1], 0));
-                }
-                if (r128)
-                    fwq_update_kernel<true, 3, 4><<<T + (te - tb), 512, 0, cs>>>(d, ld, P, k0, T, tb,
-                                                                                K1, nullptr, te);
-                else
-                    FW_UPDATE(true, 3, T + (te - tb), cs, d, ld, P, k0, T, tb, K1, nullptr, te);
-                SYM_HIP(hipGetLastError());
-                if ((rc = make(k + 1))) goto out;
-            }
-        }
-        } /* one-deep rounds */
-        SYM_HIP(hipEventRecord(sc->xs_done[0], sc->xs));
-        SYM_HIP(hipStreamWaitEvent(st, sc->xs_done[0], 0));
-        /* fill the tiles this rank does not keep: transposes from their keepers */
-        {
-            size_t nloc = 0;
-            size_t* scount = (size_t*)calloc((size_t)R, sizeof(size_t));
-            size_t* rcount = (size_t*)calloc((size_t)R, sizeof(size_t));
-            if (!scount || !rcount) {
-                free(scount);
-                free(rcount);
-                SYM_FAIL(SRT_E_NOMEM);
-            }
-            for (int q = 0; q < R; q++) {
-                for (int I = tb; I < te; I++) /* this rank keeps (I, J), J in q's rows */
-                    for (int J = qtb[q]; J < qte[q]; J++)
-                        if (I != J && sym_kept(I, J)) (q == me ? nloc : scount[q])++;
-                if (q != me)
-                    for (int I = qtb[q]; I < qte[q]; I++) /* q keeps (I, J), J in this rank's rows */
-                        for (int J = tb; J < te; J++)
-                            if (sym_kept(I, J)) rcount[q]++;
-            }
-            size_t stot = 0, rtot = 0;
-            for (int q = 0; q < R; q++) {
-                stot += scount[q];
-                rtot += rcount[q];
-            }
-            const size_t npairs = nloc + stot + rtot;
-            uint32_t* hp = (uint32_t*)malloc((npairs + 1) * sizeof(uint32_t));
-            uint32_t* dp = NULL;
-            u16* fsend = NULL;
-            u16* frecv = NULL;
-            const size_t tile = 128 * 128;
-            bool fok = hp && hipMalloc(&dp, (npairs + 1) * sizeof(uint32_t)) == hipSuccess &&
-                       hipMalloc(&fsend, (stot + 1) * tile * sizeof(u16)) == hipSuccess &&
-                       hipMalloc(&frecv, (rtot + 1) * tile * sizeof(u16)) == hipSuccess;
-            if (fok) {
-                /* layout of hp: local pairs, then send pairs by peer, then receive pairs by peer */
-                size_t o = 0;
-                for (int I = tb; I < te; I++)
-                    for (int J = tb; J < te; J++)
-                        if (I != J && sym_kept(I, J)) hp[o++] = ((uint32_t)I << 16) | (uint32_t)J;
-                for (int q = 0; q < R; q++)
-                    if (q != me)
-                        for (int I = tb; I < te; I++)
-                            for (int J = qtb[q]; J < qte[q]; J++)
-                                if (sym_kept(I, J)) hp[o++] = ((uint32_t)I << 16) | (uint32_t)J;
-                for (int q = 0; q < R; q++)
-                    if (q != me)
-                        for (int I = qtb[q]; I < qte[q]; I++)
-                            for (int J = tb; J < te; J++)
-                                if (sym_kept(I, J)) hp[o++] = ((uint32_t)I << 16) | (uint32_t)J;
-                fok = hipMemcpyAsync(dp, hp, npairs * sizeof(uint32_t), hipMemcpyHostToDevice, st) ==
-                      hipSuccess;
-                /* the copy reads pageable host memory: finish it before hp is freed */
-                fok = fok && hipStreamSynchronize(st) == hipSuccess;
-            }
-            if (fok) {
-                if (nloc) sym_fill_local_kernel<<<(unsigned)nloc, 256, 0, st>>>(d, ld, tb, dp);
-                if (stot)
-                    sym_fill_pack_kernel<<<(unsigned)stot, 256, 0, st>>>(d, ld, tb, dp + nloc, fsend);
-                size_t so = 0, ro = 0;
-                for (int q = 0; q < R; q++) {
-                    sp[q] = fsend + so * tile;
-                    sbytes[q] = q == me ? 0 : scount[q] * tile * sizeof(u16);
-                    rp[q] = frecv + ro * tile;
-                    rbytes[q] = q == me ? 0 : rcount[q] * tile * sizeof(u16);
-                    so += q == me ? 0 : scount[q];
-                    ro += q == me ? 0 : rcount[q];
-                }
-                fok = hipGetLastError() == hipSuccess;
-                if (fok && srt_comm_is_solo(comm)) /* timing only: see grecv */
-                    fok = hipMemsetD16Async((hipDeviceptr_t)frecv, 3, (rtot + 1) * tile, st) ==
-                          hipSuccess;
-                if (fok && (rc = srt_coll_exchange(comm, sp, sbytes, rp, rbytes, st))) fok = false;
-                if (fok && rtot)
-                    sym_fill_unpack_kernel<<<(unsigned)rtot, 256, 0, st>>>(d, ld, tb,
-                                                                          dp + nloc + stot, frecv);
-                fok = fok && hipGetLastError() == hipSuccess &&
-                      hipStreamSynchronize(st) == hipSuccess;
-            }
-            if (dp) (void)hipFree(dp);
-            if (fsend) (void)hipFree(fsend);
-            if (frecv) (void)hipFree(frecv);
-            free(hp);
-            free(scount);
-            free(rcount);
-            if (!fok) {
-                if (!rc) {
-                    srt_set_error("sharded symmetric FW: final fill failed");
-                    rc = SRT_E_DEVICE;
-                }
-                goto out;
-            }
-        }
-        SYM_HIP(hipMemsetAsync(flags[dev], 0, 2 * sizeof(int), st));
-        if (nrows > 0)
-            fw16_finish_kernel<<<dim3(srt_ceil_div(ld, 2048), nrows), 256, 0, st>>>(
-                n, ld, row0, d, lat_rows, flags[dev], CAP_F);
-        SYM_HIP(hipGetLastError());
-        int hf[2] = {0, 0};
-        SYM_HIP(hipMemcpyAsync(hf, flags[dev], 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-        SYM_HIP(hipStreamSynchronize(st));
-        *exact = hf[0] ? 0 : 1;
-        fw16_small[dev] = hf[1] ? 0 : 1;
+    const size_t npairs = nloc + stot + rtot, tile = 128 * 128;
+    SRT_HIPCHK(hipMalloc(&b.dp, (npairs + 1) * sizeof(uint32_t)));
+    SRT_HIPCHK(hipMalloc(&b.fsend, (stot + 1) * tile * sizeof(u16)));
+    SRT_HIPCHK(hipMalloc(&b.frecv, (rtot + 1) * tile * sizeof(u16)));
+    /* layout of hp: local pairs, then send pairs by peer, then receive pairs by peer */
+    std::vector<uint32_t> hp;
+    hp.reserve(npairs + 1);
+    for (int I = tb; I < te; I++)
+        for (int J = tb; J < te; J++)
+            if (I != J && sym_kept(I, J)) hp.push_back(pair(I, J));
+    for (int q = 0; q < R; q++)
+        if (q != me)
+            for (int I = tb; I < te; I++)
+                for (int J = qtb[q]; J < qte[q]; J++)
+                    if (sym_kept(I, J)) hp.push_back(pair(I, J));
+    for (int q = 0; q < R; q++)
+        if (q != me)
+            for (int I = qtb[q]; I < qte[q]; I++)
+                for (int J = tb; J < te; J++)
+                    if (sym_kept(I, J)) hp.push_back(pair(I, J));
+    SRT_HIPCHK(hipMemcpyAsync(b.dp, hp.data(), npairs * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    /* the copy reads pageable host memory: finish it before hp goes */
+    SRT_HIPCHK(hipStreamSynchronize(st));
+    if (nloc) sym_fill_local_kernel<<<(unsigned)nloc, 256, 0, st>>>(d, ld, tb, b.dp);
+    if (stot) sym_fill_pack_kernel<<<(unsigned)stot, 256, 0, st>>>(d, ld, tb, b.dp + nloc, b.fsend);
+    std::vector<void*> sp(R), rp(R);
+    std::vector<size_t> sbytes(R), rbytes(R);
+    size_t so = 0, ro = 0;
+    for (int q = 0; q < R; q++) {
+        sp[q] = b.fsend + so * tile;
+        sbytes[q] = q == me ? 0 : scount[q] * tile * sizeof(u16);
+        rp[q] = b.frecv + ro * tile;
+        rbytes[q] = q == me ? 0 : rcount[q] * tile * sizeof(u16);
+        so += q == me ? 0 : scount[q];
+        ro += q == me ? 0 : rcount[q];
     }
-out:
-#undef SYM_HIP
-#undef SYM_FAIL
-    (void)hipStreamSynchronize(cs);
-    (void)hipStreamSynchronize(sc->ms);
-    (void)hipStreamSynchronize(st);
-    if (tl) (void)hipFree(tl);
-    if (down) (void)hipFree(down);
-    if (grecv) (void)hipFree(grecv);
-    free(cnt);
-    free(sp);
-    free(rp);
-    free(sbytes);
-    free(rbytes);
-    free(qtb);
-    free(qte);
-    free(own);
-    free(hkept);
-    return rc;
+    SRT_HIPCHK(hipGetLastError());
+    if (srt_comm_is_solo(b.comm)) /* timing only: see grecv */
+        SRT_HIPCHK(hipMemsetD16Async((hipDeviceptr_t)b.frecv, 3, (rtot + 1) * tile, st));
+    const int rc = srt_coll_exchange(b.comm, sp.data(), sbytes.data(), rp.data(), rbytes.data(), st);
+    if (rc) return rc;
+    if (rtot)
+        sym_fill_unpack_kernel<<<(unsigned)rtot, 256, 0, st>>>(d, ld, tb, b.dp + nloc + stot, b.frecv);
+    SRT_HIPCHK(hipGetLastError());
+    SRT_HIPCHK(hipStreamSynchronize(st));
+    return SRT_OK;
 }
 
 int srt_fw16_build_sym_sharded(const srt_comm* comm, int n, int ld, int row0, int nrows,
@@ -1990,13 +1705,41 @@ int srt_fw16_build_sym_sharded(const srt_comm* comm, int n, int ld, int row0, in
                       "most %d tile columns", SYM_TMAX);
         return SRT_E_ARG;
     }
-    /* 128-pivot rounds with the 8-wave update (a 256-pivot form measured slower at N = 8: 57.6
-     * vs 45.9 ms for one rank; 64-pivot rounds slower still) */
-    const int rp = 128;
-    g_sharded_rp = rp;
-    return fw16_build_sym_sharded(comm, n, ld, row0, nrows, w_rows, lat_rows, st, evp, exact, rp);
+    const int dev = srt_state_slot();
+    /* the rank's rows, then the two panel buffers */
+    int rc = fw16_ensure(dev, (size_t)nrows * ld + 2 * (size_t)128 * ld);
+    if (rc) return rc;
+    fw16_sched* sc;
+    if ((rc = sched_get(&sc, dev))) return rc;
+    sym_build b;
+    b.comm = comm;
+    b.R = srt_comm_size(comm);
+    b.me = srt_comm_rank(comm);
+    b.ld = ld;
+    b.T = ld / 128;
+    b.row0 = row0;
+    b.tb = row0 / 128;
+    b.te = (row0 + nrows) / 128;
+    b.sc = sc;
+    b.st = st;
+    b.evp = evp;
+    b.d = fw16_bufs[dev];
+    b.pbuf[0] = b.d + (size_t)nrows * ld;
+    b.pbuf[1] = b.pbuf[0] + (size_t)128 * ld;
+    if ((rc = sym_plan(b))) return rc;
+    if (nrows > 0)
+        fw16_init_kernel<<<dim3(srt_ceil_div(ld, 2048), nrows), 256, 0, st>>>(n, ld, row0, w_rows, b.d,
+                                                                           CAP_F);
+    SRT_HIPCHK(hipGetLastError());
+    SRT_HIPCHK(hipEventRecord(sc->init_done, st));
+    SRT_HIPCHK(hipStreamWaitEvent(sc->cs, sc->init_done, 0));
+    SRT_HIPCHK(hipStreamWaitEvent(sc->xs, sc->init_done, 0));
+    if ((rc = sym_rounds_sharded(b))) return rc;
+    SRT_HIPCHK(hipEventRecord(sc->xs_done[0], sc->xs));
+    SRT_HIPCHK(hipStreamWaitEvent(st, sc->xs_done[0], 0));
+    if ((rc = sym_fill(b))) return rc;
+    return fw16_finish(n, ld, row0, nrows, b.d, lat_rows, CAP_F, st, exact);
 }
-int srt_fw16_sharded_round_pivots(void) { return g_sharded_rp; }
 
 static int fw16_square(int n, int ld, const uint32_t* w, uint32_t* lat, hipStream_t st,
                        evpool_t* evp, int* exact);
@@ -2016,49 +1759,41 @@ int srt_fw16_levels(const srt_comm* comm, int n, int ld, int row0, int nrows, in
 
 int srt_fw16_build(int n, int ld, int row0, int nrows, const uint32_t* w_rows, uint32_t* lat_rows,
                    hipStream_t st, evpool_t* evp, srt_owner_fn owner_of, srt_panel_bcast_fn bcast,
-                   void* ctx, int rank, int fm, int* sym, int* exact) {
+                   void* ctx, int rank, int fm, int symmetric, int* enc, int* exact) {
     if (ld % 128 || nrows % 128 || row0 % 128) {
         srt_set_error("u16 FW needs ld and the row shard to be multiples of 128");
         return SRT_E_ARG;
     }
+    int enc_unused;
+    if (!enc) enc = &enc_unused;
+    const bool whole = !bcast && !owner_of && row0 == 0 && nrows == ld; /* one GPU, every row */
     /* small matrices on one GPU (ld <= 2048, C2's 1,000 vertices): min-plus squaring to a fixed
      * point instead of ld / 64 latency-bound FW rounds; SRT_FORM square=0 keeps the rounds */
-    if (fm && !bcast && !owner_of && row0 == 0 && nrows == ld && ld <= 2048 &&
-        srt_form_int("square", 1) != 0) {
-        if (sym) *sym = 5;
+    if (fm && whole && ld <= 2048 && srt_form_int("square", 1) != 0) {
+        *enc = SRT_DENC_SQUARE;
         return fw16_square(n, ld, w_rows, lat_rows, st, evp, exact);
     }
-    u16** bufs = fw16_bufs;
-    size_t* caps = fw16_caps;
-    int** flags = fw16_flags;
     const int dev = srt_state_slot(); /* the device, or this virtual rank's slot */
-    const size_t need = (size_t)nrows * ld + 2 * (size_t)KB * ld;
-    if (caps[dev] < need) {
-        if (bufs[dev]) SRT_HIPCHK(hipFree(bufs[dev]));
-        SRT_HIPCHK(hipMalloc(&bufs[dev], need * sizeof(u16)));
-        caps[dev] = need;
-    }
-    if (!flags[dev]) SRT_HIPCHK(hipMalloc(&flags[dev], 2 * sizeof(int)));
-    fw16_sched* sc;
-    int rc = sched_get(&sc, dev);
+    /* the shard's rows, then two receive panels (every round form below fits in this) */
+    int rc = fw16_ensure(dev, (size_t)nrows * ld + 2 * (size_t)KB * ld);
     if (rc) return rc;
-    const bool lookahead = bcast != NULL;
+    fw16_sched* sc;
+    if ((rc = sched_get(&sc, dev))) return rc;
     /* upper-triangle rounds: undirected graph, f16-compare path, the whole matrix on one GPU */
-    const bool want_sym = sym && *sym && srt_form_int("sym", 1) != 0;
-    if (sym) *sym = 0;
-    if (want_sym && fm && !bcast && !owner_of && row0 == 0 && nrows == ld) {
+    if (symmetric && fm && whole && srt_form_int("sym", 1) != 0) {
         /* two update streams once the rounds are long enough to hide their event waits, with
          * 256-pivot rounds (128 where ld is not a multiple of 256): with the update's compute loop
          * at ~85% of the issue model, the per-tile C load, row sums, staging and store are what is
          * left to amortize, so the longest rounds measured fastest */
-        const bool two = ld >= 8192;
-        const int rp = two ? (ld % 256 == 0 ? 256 : 128) : 64;
-        *sym = rp == 256 ? 4 : rp == 128 ? 3 : two ? 2 : 1;
-        return fw16_build_sym(n, ld, w_rows, lat_rows, st, evp, exact, two, rp);
+        const int rp = ld < 8192 ? 64 : ld % 256 == 0 ? 256 : 128;
+        *enc = rp == 256 ? SRT_DENC_F16CMP_SYM256 : rp == 128 ? SRT_DENC_F16CMP_SYM128 : SRT_DENC_F16CMP_SYM;
+        return fw16_build_sym(n, ld, w_rows, lat_rows, st, evp, exact, rp);
     }
+    *enc = fm ? SRT_DENC_F16CMP : SRT_DENC_U16;
+    const bool lookahead = bcast != NULL;
     hipStream_t cs = lookahead ? sc->cs : st;
-    u16* d = bufs[dev];
-    u16* pbuf[2] = {bufs[dev] + (size_t)nrows * ld, bufs[dev] + (size_t)nrows * ld + (size_t)KB * ld};
+    u16* d = fw16_bufs[dev];
+    u16* pbuf[2] = {d + (size_t)nrows * ld, d + (size_t)nrows * ld + (size_t)KB * ld};
     const uint32_t cap = fm ? CAP_F : CAP_U;
     auto panel = fm ? fw16_panel_kernel<true, false> : fw16_panel_kernel<false, false>;
     /* the update of round k0 on this shard's tile rows (i0, skip as in tile_row) */
@@ -2128,17 +1863,7 @@ int srt_fw16_build(int n, int ld, int row0, int nrows, const uint32_t* w_rows, u
         if (lookahead) SRT_HIPCHK(hipEventRecord(sc->upd_done[k & 1], st));
         if (next && skip < 0 && (rc = produce(k + 1))) return rc;
     }
-    SRT_HIPCHK(hipMemsetAsync(flags[dev], 0, 2 * sizeof(int), st));
-    if (nrows > 0)
-        fw16_finish_kernel<<<dim3(srt_ceil_div(ld, 2048), nrows), 256, 0, st>>>(
-            n, ld, row0, d, lat_rows, flags[dev], cap);
-    SRT_HIPCHK(hipGetLastError());
-    int hf[2] = {0, 0};
-    SRT_HIPCHK(hipMemcpyAsync(hf, flags[dev], 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-    SRT_HIPCHK(hipStreamSynchronize(st));
-    *exact = hf[0] ? 0 : 1;
-    fw16_small[dev] = hf[1] ? 0 : 1;
-    return SRT_OK;
+    return fw16_finish(n, ld, row0, nrows, d, lat_rows, cap, st, exact);
 }
 
 /* ---- distance rows of a few sources on a dense graph (no all-pairs FW) -------------------- */
@@ -2294,13 +2019,8 @@ __global__ void sq_reduce_kernel(size_t count, int nq, const u16* __restrict__ p
 static int fw16_square(int n, int ld, const uint32_t* w, uint32_t* lat, hipStream_t st,
                        evpool_t* evp, int* exact) {
     const int dev = srt_state_slot();
-    const size_t need = (size_t)ld * ld + 2 * (size_t)KB * ld;
-    if (fw16_caps[dev] < need) {
-        if (fw16_bufs[dev]) SRT_HIPCHK(hipFree(fw16_bufs[dev]));
-        SRT_HIPCHK(hipMalloc(&fw16_bufs[dev], need * sizeof(u16)));
-        fw16_caps[dev] = need;
-    }
-    if (!fw16_flags[dev]) SRT_HIPCHK(hipMalloc(&fw16_flags[dev], 2 * sizeof(int)));
+    const int erc = fw16_ensure(dev, (size_t)ld * ld + 2 * (size_t)KB * ld);
+    if (erc) return erc;
     u16* d = fw16_bufs[dev];
     int* flags = fw16_flags[dev];
     const int T = ld / 128;
@@ -2379,13 +2099,7 @@ static int fw16_square(int n, int ld, const uint32_t* w, uint32_t* lat, hipStrea
             break;
         }
     }
-    if (!finished) {
-        SRT_HIPCHK(hipMemsetAsync(flags, 0, 2 * sizeof(int), st));
-        fw16_finish_kernel<<<dim3(srt_ceil_div(ld, 2048), ld), 256, 0, st>>>(n, ld, 0, d, lat, flags, CAP_F);
-        SRT_HIPCHK(hipGetLastError());
-        SRT_HIPCHK(hipMemcpyAsync(hf, flags, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-        SRT_HIPCHK(hipStreamSynchronize(st));
-    }
+    if (!finished) return fw16_finish(n, ld, 0, ld, d, lat, CAP_F, st, exact);
     *exact = hf[0] ? 0 : 1;
     fw16_small[dev] = hf[1] ? 0 : 1;
     return SRT_OK;

@@ -149,19 +149,19 @@ static inline int evpool_sum(evpool_t* p, hipEvent_t last, srt_build_stats* stat
 
 typedef int (*srt_panel_bcast_fn)(void* ctx, void* panel, size_t bytes, int owner, hipStream_t st);
 typedef int (*srt_owner_fn)(void* ctx, int k0);
-/* packed-u16 Floyd-Warshall over a row shard (fw16.hip). d16: nrows x ld u16. *sym = 1 on input
- * (undirected, symmetric w) lets a single-shard f16-compare build update only upper-triangle tiles;
- * on output it says whether that form ran (sym may be NULL). fm = 1 selects the
- * f16-compare instruction mix (cap 0x3DFF), fm = 0 the v_pk_min_u16 mix (cap 0x7FFF). Returns
- * SRT_OK and *exact = 1 when every distance is below the cap (else the caller reruns with the
- * next wider path). lat_rows receives the distances widened to u32 quanta. */
 /* row-sharded symmetric rounds (undirected, f16-compare path, >= 2 ranks; fw16.hip) */
 int srt_fw16_build_sym_sharded(const srt_comm* comm, int n, int ld, int row0, int nrows,
                                const uint32_t* w_rows, uint32_t* lat_rows, hipStream_t st,
                                evpool_t* evp, int* exact);
+/* packed-u16 Floyd-Warshall over a row shard (fw16.hip). d16: nrows x ld u16. symmetric = 1
+ * (undirected, symmetric w) lets a single-shard f16-compare build update only upper-triangle
+ * tiles. fm = 1 selects the f16-compare instruction mix (cap 0x3DFF), fm = 0 the v_pk_min_u16 mix
+ * (cap 0x7FFF). *enc (may be NULL) receives the SRT_DENC_* value of the form that ran. Returns
+ * SRT_OK and *exact = 1 when every distance is below the cap (else the caller reruns with the
+ * next wider path). lat_rows receives the distances widened to u32 quanta. */
 int srt_fw16_build(int n, int ld, int row0, int nrows, const uint32_t* w_rows, uint32_t* lat_rows,
                    hipStream_t st, evpool_t* evp, srt_owner_fn owner_of, srt_panel_bcast_fn bcast,
-                   void* ctx, int rank, int fm, int* sym, int* exact);
+                   void* ctx, int rank, int fm, int symmetric, int* enc, int* exact);
 /* levels.hip: distance rows of the local sources by bit-parallel Dial levels (see there) */
 int srt_levels_build(const srt_comm* comm, int n, int ld, int row0, int nrows, int directed,
                      const uint32_t* w_rows, const double* r_rows, uint32_t* lat_rows, double fw_ms,
@@ -213,12 +213,13 @@ enum {
     SRT_DENC_U32 = 1,
     SRT_DENC_U16 = 2,
     SRT_DENC_F16CMP = 3,
-    SRT_DENC_F16CMP_SYM = 4,
-    SRT_DENC_F16CMP_SYM2 = 5, /* one GPU, upper triangle on two update streams */
-    SRT_DENC_F16CMP_SYM128 = 6, /* 5 with 128-pivot rounds (8-wave update, 4 stages per tile) */
-    SRT_DENC_F16CMP_SYM256 = 7, /* 5 with 256-pivot rounds (8 stages per tile) */
-    SRT_DENC_F16CMP_SYMSH128 = 8, /* 4 (row-sharded, >= 2 ranks) with 128-pivot rounds */
-    SRT_DENC_F16CMP_SYMSH256 = 9, /* 4 (row-sharded) with 256-pivot rounds */
+    SRT_DENC_F16CMP_SYM = 4,      /* one GPU, upper triangle, 64-pivot rounds on one stream */
+    SRT_DENC_F16CMP_SYM2 = 5,     /* retired: 64-pivot rounds on two update streams */
+    SRT_DENC_F16CMP_SYM128 = 6,   /* one GPU, upper triangle on two update streams, 128-pivot
+                                   * rounds (4 stages per tile) */
+    SRT_DENC_F16CMP_SYM256 = 7,   /* the same with 256-pivot rounds (8 stages per tile) */
+    SRT_DENC_F16CMP_SYMSH128 = 8, /* row-sharded kept tiles (>= 2 ranks), 128-pivot rounds */
+    SRT_DENC_F16CMP_SYMSH256 = 9, /* retired: row-sharded 256-pivot rounds */
     SRT_DENC_ROWS = 10,           /* a few source rows by Bellman-Ford passes, no FW */
     SRT_DENC_SQUARE = 11,         /* ld <= 2048 on one GPU: min-plus squaring to a fixed point */
     SRT_DENC_LEVELS = 12          /* bit-parallel Dial levels (levels.hip), no FW rounds */
@@ -227,8 +228,6 @@ int srt_dense_rows_build_device(int32_t n, int32_t ld, int32_t nsub, const int32
                                 const uint32_t* w, const double* r, uint32_t* lat_rows,
                                 double* rel_rows, double* lms_rows, uint64_t quantum_ns,
                                 int32_t directed, hipStream_t st, srt_build_stats* stats, int* used);
-/* pivots per round of this thread's last srt_fw16_build_sym_sharded (64 or 128) */
-int srt_fw16_sharded_round_pivots(void);
 /* distance rows of nsub sources on a dense graph by Bellman-Ford passes on u16 quanta (fw16.hip);
  * w16: ld x ld scratch, ds: (nsub rounded up to 128) x ld scratch, lat_rows: nsub x ld u32 */
 int srt_fw16_rows(int n, int ld, int nsub, const int32_t* dverts, const uint32_t* w, uint16_t* w16,

@@ -170,7 +170,9 @@ def _dense_worker(rank, R, port, n, seed, q):
 
 
 def _dense_sym_worker(rank, R, port, n, seed, q, rp=KB):
-    """The row-sharded symmetric rounds of fw16.hip fw16_build_sym_sharded, distances only: each
+    """The row-sharded symmetric rounds of fw16.hip srt_fw16_build_sym_sharded (its band
+    broadcast is sym_send, its closure sym_close; the library runs the rp = 128 form only, the
+    64-pivot model stays as the plainer statement of the same rounds), distances only: each
     rank keeps one orientation of every 128-tile pair (sym_kept); every rank broadcasts the
     pivot-panel blocks it holds (its kept row blocks, or transposed 64 x 128 slices of its tiles
     in the pivot column), every rank closes the diagonal block and the row panel itself and the

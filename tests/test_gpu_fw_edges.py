@@ -22,6 +22,7 @@ import fw_graphs as fg
 import level_graphs as lg
 import oracle
 from level_graphs import check_tables
+from shadow_amd import graphs
 from shadow_amd._lib import ALGO_AUTO, SRT_INF
 from shadow_amd.topology import build_tables_subset
 
@@ -91,6 +92,36 @@ def test_cap_edges_virtual_ranks(gpu, monkeypatch, ranks, directed, e):
     want = _tier(e, 3 if directed else 8)
     assert st.dist_enc == want, (st.dist_enc, want)
     check_tables(g, lat, rel, f"x{ranks} {'directed ' if directed else ''}E={e}")
+
+
+def _ring_with_chords(n, hop_ms=1):
+    """test_dense_distance_encoding_tiers's graph on n vertices: an undirected ring with hop
+    latencies hop_ms / hop_ms + 1 alternating, plus 12 chords of hop_ms * n // 3."""
+    rng = np.random.default_rng(hop_ms)
+    src = list(range(n))
+    dst = [(i + 1) % n for i in range(n)]
+    lat = [(hop_ms + (i % 2)) * lg.MS for i in range(n)]
+    for _ in range(12):
+        a, b = (int(x) for x in rng.choice(n, 2, replace=False))
+        src.append(a)
+        dst.append(b)
+        lat.append(int(hop_ms * n // 3) * lg.MS)
+    loss = rng.integers(0, 100, len(src)) * 1e-4
+    return graphs.Graph(n, 0, np.array(src, np.int32), np.array(dst, np.int32),
+                        np.array(lat, np.int64), loss)
+
+
+@pytest.mark.parametrize("n", [100, 200])
+def test_sharded_rounds_with_one_or_two_bands(gpu, monkeypatch, n):
+    """The row-sharded symmetric rounds where the prologue sends every band there is: n = 100 is
+    ld = 128, one band and one round, and the second of the two ranks holds no rows; n = 200 is
+    ld = 256, two bands. Distances stay below ~150 quanta, so the f16-compare tier serves both."""
+    _form(monkeypatch)
+    monkeypatch.setenv("SRT_VIRTUAL_RANKS", "2")
+    g = _ring_with_chords(n)
+    lat, rel, st = lg.build(g, ngpus=1)
+    assert st.dist_enc == 8, st.dist_enc
+    check_tables(g, lat, rel, f"ring n={n} x2")
 
 
 def _check_subset(g, verts, lat, rel, what):
