@@ -14,6 +14,19 @@
  * distances u32 quanta with SRT_INF = 0x7FFFFFFF (a + b never wraps: both operands <= INF),
  * reliabilities f64. No MFMA: min-plus is not an FMA contraction; the hot loop is
  * v_add_u32 + v_min3_u32 over 4x4 register blocks fed by ds_read_b128 from LDS.
+ *
+ * The host half, beneath the kernels each part launches:
+ *   rel_*_launch, rel_level_rows, rel_fw_rows   the reliability passes, one function per caller
+ *   dbuf, dense_ws, ws_get       the buffers of a state slot; they only grow
+ *   dense_build, post_state      one build's arguments, and what its post pass decided (stack)
+ *   dense_post                   FW post pass: ess_lists -> inarcs_transpose (directed) ->
+ *                                pred_search -> pred_rows -> rel_fw_rows -> ess_total
+ *   dense_post_levels            a level build's post pass (srt_levels_pred, rel_pk / rel_level_rows)
+ *   dense_finish_rows            the diagonal rule, the post pass's device counters into the stats
+ *   srt_dense_rows_build_device  a few source rows, no FW
+ *   dense_build_run              THE build: dense_distances (levels -> u16 tiers -> u32 rounds),
+ *                                dense_tables (post, finish, ms rows), the stats; comm NULL = one
+ *                                GPU. srt_dense_build_{device,sharded}_ms check arguments and call it.
  */
 #include "srt_device.h"
 
@@ -331,17 +344,6 @@ static int fw_shard_part(uint32_t* D, int ld, int row0, int nrows, const uint32_
     return SRT_OK;
 }
 
-int srt_dense_fw_device(int32_t n, int32_t ld, uint32_t* d, hipStream_t st, evpool_t* evp) {
-    (void)n;
-    for (int k0 = 0; k0 < ld; k0 += B) {
-        uint32_t* P = d + (size_t)k0 * ld;
-        int rc = fw_owner_part(d, ld, 0, ld, P, k0, st);
-        if (!rc) rc = fw_shard_part(d, ld, 0, ld, P, k0, st, evp);
-        if (rc) return rc;
-    }
-    return SRT_OK;
-}
-
 /* ------------------------------------------------------------------------------------------ */
 /* Essential arcs: (u,t) with W[u][t] == D[u][t] (u != t). Every tight predecessor of any      */
 /* (s,t) is essential: D[s][u] + W[u][t] = D[s][t] <= D[s][u] + D[u][t] forces D[u][t] = W.    */
@@ -515,7 +517,7 @@ __global__ void arc_transpose_fill(int n, const int32_t* __restrict__ ptr,
 /* ------------------------------------------------------------------------------------------ */
 /* out[c][r] = in[r][c]; BM (block-major, 64 or 128): out[r / BM][c][r % BM], ldo = the stride of
  * a BM-row block, so each block's transpose is one contiguous slab */
-template <typename T, typename TO = T, int BM = 0, bool NTS = false>
+template <typename T, typename TO = T, int BM = 0>
 __global__ __launch_bounds__(256) void transpose_kernel(int rows, int cols, const T* __restrict__ in,
                                                         size_t ldi, TO* __restrict__ out, size_t ldo) {
     __shared__ T tile[64][65];
@@ -536,8 +538,6 @@ __global__ __launch_bounds__(256) void transpose_kernel(int rows, int cols, cons
         if (r < rows && c < cols) {
             if constexpr (BM != 0)
                 out[(size_t)(r / BM) * ldo + (size_t)c * BM + (r % BM)] = (TO)tile[tx][a];
-            else if constexpr (NTS) /* streaming: rows read once, by a later pass */
-                __builtin_nontemporal_store((TO)tile[tx][a], out + (size_t)c * ldo + r);
             else
                 out[(size_t)c * ldo + r] = (TO)tile[tx][a];
         }
@@ -564,7 +564,7 @@ static __device__ __forceinline__ void add_ties(unsigned long long* out, uint32_
     if ((threadIdx.x & 63) == 0 && v) atomicAdd(out, v);
 }
 
-template <typename T, bool UR, bool TIES>
+template <typename T, bool TIES>
 __global__ __launch_bounds__(256) void pred_cols_kernel(int n, int row0, int nloc, int ldT,
                                                         size_t bsD, const T* __restrict__ DT,
                                                         const int32_t* __restrict__ iptr,
@@ -574,8 +574,8 @@ __global__ __launch_bounds__(256) void pred_cols_kernel(int n, int row0, int nlo
                                                         double* __restrict__ rT, int nsb,
                                                         int tch, int tper, int sorted,
                                                         unsigned long long* __restrict__ ties) {
-    /* UR: write the predecessor vertex and the reliability of its arc (predT, rT) for the
-     * level-order pass; otherwise the arc index.
+    /* Writes the predecessor vertex and the reliability of its arc (predT, rT) for the
+     * level-order pass.
      * sorted: t's in-arc list is in ascending u (undirected: the out-lists of the ballot-compacted
      * essential arcs); the transposed lists of a directed graph are not, and key on u itself.
      * Narrow distances (u8/u16: D < 2^16) and in-degrees < 2^16 pack the key (D[s][u], arc rank
@@ -660,13 +660,9 @@ __global__ __launch_bounds__(256) void pred_cols_kernel(int n, int row0, int nlo
         if (TIES && valid && s != t) nties += tie;
         if (valid) {
             const size_t o = (size_t)t * ldT + sl;
-            if (UR) {
-                const bool has = s != t && bk >= 0;
-                predT[o] = has ? (int32_t)uw[bk].x : -1;
-                rT[o] = has ? ar[bk] : 0.0;
-            } else {
-                predT[o] = (s == t) ? -1 : bk;
-            }
+            const bool has = s != t && bk >= 0;
+            predT[o] = has ? (int32_t)uw[bk].x : -1;
+            rT[o] = has ? ar[bk] : 0.0;
         }
     }
     if (TIES) add_ties(ties, nties);
@@ -674,8 +670,9 @@ __global__ __launch_bounds__(256) void pred_cols_kernel(int n, int row0, int nlo
 
 /* Byte distances, two sources per lane: a wave covers a 128-source block, one 128-B line of its
  * block-major slab (DT[s / 128][u][s % 128], 4 MB at n = 32,768) per candidate arc. Same keys and
- * outputs as pred_cols_kernel<uint8_t, true> for each of the lane's two sources. */
-template <int U, bool TIES>
+ * outputs as pred_cols_kernel for each of the lane's two sources; U = 16 candidate arcs in flight
+ * per step. */
+template <bool TIES>
 __global__ __launch_bounds__(256) void pred_cols2_kernel(int n, int row0, int nloc, int ldT,
                                                          size_t bsD, const uint8_t* __restrict__ DT,
                                                          const int32_t* __restrict__ iptr,
@@ -690,6 +687,7 @@ __global__ __launch_bounds__(256) void pred_cols2_kernel(int n, int row0, int nl
     if (sb >= nsb) return;
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    constexpr int U = 16;
     const int sl = sb * 128 + 2 * lane;
     const int s = row0 + sl;
     const bool v0 = sl < nloc && s < n, v1 = sl + 1 < nloc && s + 1 < n;
@@ -799,7 +797,6 @@ __global__ void pack_uk_kernel(int n, const int32_t* __restrict__ iptr, const in
     }
 }
 
-template <int U, bool NT>
 __global__ __launch_bounds__(256) void pred_cols3_kernel(int n, int row0, int nloc, int ldT,
                                                          size_t bsD, const uint8_t* __restrict__ DT,
                                                          const int32_t* __restrict__ iptr,
@@ -813,6 +810,7 @@ __global__ __launch_bounds__(256) void pred_cols3_kernel(int n, int row0, int nl
     if (sb >= nsb) return;
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    constexpr int U = 16; /* candidate arcs in flight per step */
     const int sl = sb * 128 + 2 * lane;
     const int s = row0 + sl;
     const bool v0 = sl < nloc && s < n, v1 = sl + 1 < nloc && s + 1 < n;
@@ -875,18 +873,12 @@ __global__ __launch_bounds__(256) void pred_cols3_kernel(int n, int row0, int nl
             const int32_t p0 = h0 ? (int32_t)(uk[bk0].x >> 7) : -1;
             const int32_t p1 = h1 ? (int32_t)(uk[bk1].x >> 7) : -1;
             const double r0 = h0 ? ar[bk0] : 0.0, r1 = h1 ? ar[bk1] : 0.0;
-            if constexpr (NT) {
-                /* streaming stores: the 50 MB of outputs per source block do not allocate in
-                 * L2, which holds the block's 4-MB slab */
-                __builtin_nontemporal_store(p0, predT + o);
-                __builtin_nontemporal_store(p1, predT + o + 1);
-                __builtin_nontemporal_store(r0, rT + o);
-                __builtin_nontemporal_store(r1, rT + o + 1);
-            } else {
-                *reinterpret_cast<int2*>(predT + o) = make_int2(p0, p1);
-                rT[o] = r0;
-                rT[o + 1] = r1;
-            }
+            /* streaming stores: the 50 MB of outputs per source block do not allocate in
+             * L2, which holds the block's 4-MB slab */
+            __builtin_nontemporal_store(p0, predT + o);
+            __builtin_nontemporal_store(p1, predT + o + 1);
+            __builtin_nontemporal_store(r0, rT + o);
+            __builtin_nontemporal_store(r1, rT + o + 1);
         } else {
             if (v0) {
                 predT[o] = h0 ? (int32_t)(uk[bk0].x >> 7) : -1;
@@ -972,9 +964,26 @@ __global__ __launch_bounds__(512) void rel_sweeps_kernel(int n, int ld, int row0
     if (threadIdx.x == 0) srt_max_once(max_depth, depth);
 }
 
+/* rel_sweeps_kernel over the rows still flagged in `sweep` (the row's predecessors and two bitmaps
+ * in LDS); int32 rows of n > 32768 (by index only: no srcs) take tables.hip's form */
+template <typename PT>
+static int rel_sweeps_launch(int n, int ld, int row0, int lrows, const PT* pred, double* rel,
+                             int32_t* depth, const int32_t* sweep, const int32_t* srcs,
+                             hipStream_t st) {
+    if constexpr (std::is_same_v<PT, int32_t>)
+        if (n > 32768)
+            return srt_rel_sweeps_rows(n, lrows, row0, pred, (size_t)ld, rel, (size_t)ld, sweep, depth, st);
+    const size_t lds = (size_t)n * sizeof(int32_t) + 2 * (size_t)((n + 31) / 32) * 4;
+    SRT_HIPCHK(hipFuncSetAttribute((const void*)rel_sweeps_kernel<PT>,
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    rel_sweeps_kernel<PT><<<lrows, 512, lds, st>>>(n, ld, row0, pred, rel, depth, sweep, srcs);
+    SRT_HIPCHK(hipGetLastError());
+    return SRT_OK;
+}
+
 /* Reliability in increasing-distance order, one workgroup per local source row, in place: the
- * rel row arrives holding r(pred(s,t), t) and the pred row the predecessor vertex (pred_cols
- * UR form). Every arc is >= 1 quantum, so D[s][pred] < D[s][t] and pass L (targets with
+ * rel row arrives holding r(pred(s,t), t) and the pred row the predecessor vertex (what
+ * pred_cols*_kernel write). Every arc is >= 1 quantum, so D[s][pred] < D[s][t] and pass L (targets with
  * D[s][t] == L) only reads values final since an earlier pass: each entry is formed once,
  * rel(s,t) = rel(s,pred) * r(pred,t), the left-to-right product of topology.c:1364-1365.
  * Rows whose largest distance exceeds maxl passes are flagged for rel_sweeps_kernel. */
@@ -1261,7 +1270,7 @@ __global__ __launch_bounds__(NT) void rel_tree_kernel(int n, int ld, int row0,
 template <typename LT, typename PT>
 static void rel_tree_launch(int n, int ld, int row0, int lrows, const LT* d, const PT* pred,
                             double* rel, int32_t* depth, int32_t* sweep, const int32_t* srcs,
-                            hipStream_t st, const double* rtab = nullptr, int ntab = 0) {
+                            hipStream_t st, const double* rtab, int ntab) {
     if (n <= 1024) {
         const int lds = (int)rel_tree_lds(256, 4, 1024, ntab + 1);
         (void)hipFuncSetAttribute((const void*)rel_tree_kernel<256, 4, LT, PT>,
@@ -1502,12 +1511,7 @@ static int rel_pk_launch(int n, int ld, int row0, int lrows, const uint32_t* pk,
     }
 #undef REL_PK_GO
     SRT_HIPCHK(hipGetLastError());
-    const size_t slds = (size_t)n * sizeof(int32_t) + 2 * (size_t)((n + 31) / 32) * 4;
-    SRT_HIPCHK(hipFuncSetAttribute((const void*)rel_sweeps_kernel<uint32_t>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)slds));
-    rel_sweeps_kernel<uint32_t><<<lrows, 512, slds, st>>>(n, ld, row0, pk, rel, depth, sweep, nullptr);
-    SRT_HIPCHK(hipGetLastError());
-    return SRT_OK;
+    return rel_sweeps_launch(n, ld, row0, lrows, pk, rel, depth, sweep, nullptr, st);
 }
 
 /* Rows with deep predecessor trees (metric / Tor-atlas-like graphs: ~100 hops, hundreds of distinct
@@ -1802,41 +1806,14 @@ static int rel_order_launch(int n, int ld, int row0, int lrows, const uint32_t* 
     return SRT_OK;
 }
 
-static int rel_rows_launch(int n, int ld, int row0, int lrows, const uint32_t* d, int32_t* pred,
-                           double* rel, int32_t* depth, int32_t* sweep, const int32_t* srcs,
-                           hipStream_t st, const uint8_t* l8 = nullptr,
-                           const int16_t* pred16 = nullptr, const uint32_t* pk = nullptr,
-                           const double* rtab = nullptr, int ntab = 0, uint32_t* ord = nullptr) {
-    if (lrows <= 0) return SRT_OK;
-    int rc;
-    const bool tree = n <= 32768 && srt_form_int("reltree", 1) != 0;
-    if (pk) { /* a level build's u8 rows and packed (predecessor | reliability index) rows */
-        rel_tree_launch(n, ld, row0, lrows, l8, pk, rel, depth, sweep, srcs, st, rtab, ntab);
-        SRT_HIPCHK(hipGetLastError());
-        const size_t lds = (size_t)n * sizeof(int32_t) + 2 * (size_t)((n + 31) / 32) * 4;
-        SRT_HIPCHK(hipFuncSetAttribute((const void*)rel_sweeps_kernel<uint32_t>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        rel_sweeps_kernel<uint32_t><<<lrows, 512, lds, st>>>(n, ld, row0, pk, rel, depth, sweep,
-                                                             srcs);
-        SRT_HIPCHK(hipGetLastError());
-        return SRT_OK;
-    }
-    if (pred16) { /* a level build's u8 distance rows and int16 predecessor rows (n <= 32768) */
-        rel_tree_launch(n, ld, row0, lrows, l8, pred16, rel, depth, sweep, srcs, st);
-        SRT_HIPCHK(hipGetLastError());
-        const size_t lds = (size_t)n * sizeof(int32_t) + 2 * (size_t)((n + 31) / 32) * 4;
-        SRT_HIPCHK(hipFuncSetAttribute((const void*)rel_sweeps_kernel<int16_t>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        rel_sweeps_kernel<int16_t><<<lrows, 512, lds, st>>>(n, ld, row0, pred16, rel, depth, sweep,
-                                                            srcs);
-        SRT_HIPCHK(hipGetLastError());
-        return SRT_OK;
-    }
-    if (tree && l8)
-        rel_tree_launch(n, ld, row0, lrows, l8, (const int32_t*)pred, rel, depth, sweep, srcs, st);
-    else if (tree)
-        rel_tree_launch(n, ld, row0, lrows, d, (const int32_t*)pred, rel, depth, sweep, srcs, st);
-    else if (n <= 1024) {
+/* whether rows of n targets take rel_tree_kernel (SRT_FORM reltree=0: rel_levels_kernel) */
+static bool rel_tree_on(int n) { return n <= 32768 && srt_form_int("reltree", 1) != 0; }
+
+/* rel_levels_kernel at the row's size class */
+static int rel_levels_launch(int n, int ld, int row0, int lrows, const uint32_t* d, int32_t* pred,
+                             double* rel, int32_t* depth, int32_t* sweep, const int32_t* srcs,
+                             hipStream_t st) {
+    if (n <= 1024) {
         rel_levels_kernel<256, 1024><<<lrows, 256, 2048, st>>>(n, ld, row0, d, pred, rel, 64, depth,
                                                               sweep, srcs);
     } else if (n <= 4096) {
@@ -1854,9 +1831,46 @@ static int rel_rows_launch(int n, int ld, int row0, int lrows, const uint32_t* d
                                                                   depth, sweep, srcs);
     }
     SRT_HIPCHK(hipGetLastError());
-    /* deep rows (distance range past the level passes' 64): parents only in distance order
-     * (rel_deep_kernel), then what it left (more parents than its slots) one wave per row */
-    if (tree && !srcs && !l8 && n <= 65535) {
+    return SRT_OK;
+}
+
+/* The reliability pass of a level build's u8 distance rows l8 (dense_post_levels' SRT_LVL_POST_U8),
+ * by the rows' predecessor form: int16 rows (n <= 32768), packed (predecessor | reliability index)
+ * words with the table rtab (n <= 32768), or int32 rows (n > 32768 today, where rel_tree_kernel
+ * does not apply and rel_levels_kernel reads the u32 rows d). Level order for the rows that span
+ * <= 64 quanta, the sweeps for the rest. */
+template <typename PT>
+static int rel_level_rows(int n, int ld, int row0, int lrows, const uint32_t* d, const uint8_t* l8,
+                          PT* pred, double* rel, int32_t* depth, int32_t* sweep, const double* rtab,
+                          int ntab, hipStream_t st) {
+    if (lrows <= 0) return SRT_OK;
+    constexpr bool wide = std::is_same_v<PT, int32_t>;
+    if (!wide || rel_tree_on(n)) {
+        rel_tree_launch(n, ld, row0, lrows, l8, (const PT*)pred, rel, depth, sweep, nullptr, st, rtab,
+                        ntab);
+        SRT_HIPCHK(hipGetLastError());
+    } else if constexpr (wide) {
+        const int rc = rel_levels_launch(n, ld, row0, lrows, d, pred, rel, depth, sweep, nullptr, st);
+        if (rc) return rc;
+    }
+    return rel_sweeps_launch(n, ld, row0, lrows, (const PT*)pred, rel, depth, sweep, nullptr, st);
+}
+
+/* The reliability chain of the FW post pass over u32 distance rows d and int32 predecessor rows:
+ * level order for the rows that span <= 64 quanta (rel_tree_kernel / rel_levels_kernel), the deep
+ * rows by their parents in distance order (rel_deep_kernel), what that left (more parents than its
+ * slots) one wave per row (rel_order_kernel, lists in ord), then the sweeps. */
+static int rel_fw_rows(int n, int ld, int row0, int lrows, const uint32_t* d, int32_t* pred,
+                       double* rel, int32_t* depth, int32_t* sweep, uint32_t* ord, hipStream_t st) {
+    if (lrows <= 0) return SRT_OK;
+    int rc;
+    if (!rel_tree_on(n)) {
+        if ((rc = rel_levels_launch(n, ld, row0, lrows, d, pred, rel, depth, sweep, nullptr, st)))
+            return rc;
+    } else {
+        rel_tree_launch(n, ld, row0, lrows, d, (const int32_t*)pred, rel, depth, sweep, nullptr, st,
+                        nullptr, 0);
+        SRT_HIPCHK(hipGetLastError());
         const int fixed = 8 * (ld >> 5) + 4 * DEEP_NB;
         const int cap = min(n, (160 * 1024 - 1024 - fixed) / 14) & ~63;
         const int lds = fixed + 14 * cap;
@@ -1865,20 +1879,10 @@ static int rel_rows_launch(int n, int ld, int row0, int lrows, const uint32_t* d
         rel_deep_kernel<<<lrows, DEEP_NT, lds, st>>>(n, ld, row0, lrows, d, pred, rel, cap, sweep,
                                                      depth);
         SRT_HIPCHK(hipGetLastError());
+        if ((rc = rel_order_launch<int32_t>(n, ld, row0, lrows, d, pred, rel, ord, sweep, depth, st)))
+            return rc;
     }
-    if (tree && !srcs && !l8 &&
-        (rc = rel_order_launch<int32_t>(n, ld, row0, lrows, d, pred, rel, ord, sweep, depth, st)))
-        return rc;
-    if (n <= 32768) {
-        const size_t lds = (size_t)n * sizeof(int32_t) + 2 * (size_t)((n + 31) / 32) * 4;
-        SRT_HIPCHK(hipFuncSetAttribute((const void*)rel_sweeps_kernel<int32_t>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        rel_sweeps_kernel<int32_t><<<lrows, 512, lds, st>>>(n, ld, row0, pred, rel, depth, sweep,
-                                                            srcs);
-        SRT_HIPCHK(hipGetLastError());
-        return SRT_OK;
-    }
-    return srt_rel_sweeps_rows(n, lrows, row0, pred, (size_t)ld, rel, (size_t)ld, sweep, depth, st);
+    return rel_sweeps_launch(n, ld, row0, lrows, (const int32_t*)pred, rel, depth, sweep, nullptr, st);
 }
 
 __global__ void pack_uw_kernel(int64_t arcs, const int32_t* __restrict__ col,
@@ -1897,7 +1901,7 @@ __global__ __launch_bounds__(256) void dense_diag_kernel(int n, int ld, int row0
                                                          const double* __restrict__ r,
                                                          uint32_t* __restrict__ d,
                                                          double* __restrict__ rel,
-                                                         const int32_t* __restrict__ srcs = nullptr) {
+                                                         const int32_t* __restrict__ srcs) {
     /* srcs: output row lr is source srcs[lr], whose edges are row srcs[lr] of the full w / r */
     const int lr = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (lr >= nrows) return;
@@ -1944,46 +1948,45 @@ __global__ __launch_bounds__(256) void dense_diag_kernel(int n, int ld, int row0
 /* ------------------------------------------------------------------------------------------ */
 /* host orchestration of the dense post pass (single GPU or one row shard)                    */
 /* ------------------------------------------------------------------------------------------ */
+/* a device buffer that only grows: need(count) keeps what is there while it is large enough */
+template <typename T>
+struct dbuf {
+    T* p;
+    size_t cap;
+    int need(size_t count) {
+        if (cap >= count && p) return SRT_OK;
+        if (p) SRT_HIPCHK(hipFree(p));
+        p = NULL;
+        const size_t c = count + count / 4 + 1024;
+        SRT_HIPCHK(hipMalloc((void**)&p, c * sizeof(T)));
+        cap = c;
+        return SRT_OK;
+    }
+};
+
+/* the buffers of one state slot (and its lazily created events): nothing here says what the build
+ * in flight decided -- that is post_state, on the build's stack */
 typedef struct {
-    size_t n_cap, arc_cap, tarc_cap;
-    int32_t *cnt, *ptr, *tptr, *cursor, *col, *tcol;
+    size_t n_cap; /* of cnt, ptr, tptr, cursor (n + 1 words each) */
+    int32_t *cnt, *ptr, *tptr, *cursor;
     int32_t* depth; /* [0] the deepest tree of the reliability pass, [1] the level predecessor
                      * pre-pass's overflowed buckets (read back together) */
     unsigned long long* ties; /* tied-pair count of the predecessor pass */
-    uint32_t *aw, *tw;
-    double *ar, *tr;
-    uint32_t* panel;
-    size_t panel_cap;
-    uint2* uw;
-    size_t uw_cap;
-    uint32_t* dt;   /* transpose of the local row block, then the predecessor rows */
-    int32_t* predt; /* predecessors, sources across columns */
-    size_t dt_cap, predt_cap;
-    double* rt; /* reliability of each predecessor arc, sources across columns */
-    size_t rt_cap;
+    dbuf<int32_t> col, tcol; /* the essential arcs by tail (col, aw, ar) and, directed graphs, */
+    dbuf<uint32_t> aw, tw;   /* by head (tcol, tw, tr) */
+    dbuf<double> ar, tr;
+    dbuf<uint32_t> panel;
+    dbuf<uint2> uw;
+    dbuf<uint32_t> dt;   /* transpose of the local row block, then the predecessor rows */
+    dbuf<int32_t> predt; /* predecessors, sources across columns */
+    dbuf<double> rt;     /* reliability of each predecessor arc, sources across columns */
     int32_t* h_total; /* pinned: the essential-arc total of a post pass that did not wait for it */
-    int total_pending;
     /* time_kernels: events around the level post pass's predecessor and reliability kernels,
      * read after the build's final wait (dense_finish_rows) */
     hipEvent_t kev[4];
-    int kev_on;
-    int diag_done; /* the level post pass applied the diagonal rule itself */
-    int pred16;    /* what dt holds after the level post pass, as a srt_lvl_pred_layout: I16 rows
-                    * (n <= 32768), PK_COLS: packed predecessor | reliability index words */
-    int pn_cap;    /* the level post pass took lvl_pred_near_kernel with this bucket capacity */
 } dense_ws;
 
 static dense_ws g_ws[SRT_STATE_SLOTS];
-
-static int ws_grow(void** p, size_t* cap, size_t need, size_t elem) {
-    if (*cap >= need && *p) return SRT_OK;
-    if (*p) SRT_HIPCHK(hipFree(*p));
-    *p = NULL;
-    size_t c = need + need / 4 + 1024;
-    SRT_HIPCHK(hipMalloc(p, c * elem));
-    *cap = c;
-    return SRT_OK;
-}
 
 static int ws_get(dense_ws** out, int n) {
     dense_ws* ws = &g_ws[srt_state_slot()];
@@ -2009,55 +2012,70 @@ static int ws_get(dense_ws** out, int n) {
     return SRT_OK;
 }
 
-static int grow_arcs(dense_ws* ws, size_t need) {
-    int rc;
-    size_t c1 = ws->arc_cap, c2 = ws->arc_cap, c3 = ws->arc_cap;
-    if ((rc = ws_grow((void**)&ws->col, &c1, need, sizeof(int32_t)))) return rc;
-    if ((rc = ws_grow((void**)&ws->aw, &c2, need, sizeof(uint32_t)))) return rc;
-    if ((rc = ws_grow((void**)&ws->ar, &c3, need, sizeof(double)))) return rc;
-    ws->arc_cap = c1;
-    return SRT_OK;
-}
-
 /* gather hook for sharded builds: makes the essential-arc counts / arcs global */
 typedef int (*ess_gather_fn)(void* ctx, dense_ws* ws, int n, int phase, int32_t total,
                              hipStream_t st);
 
-/* The post pass of a level build (levels.hip): the canonical predecessors and their arc
- * reliabilities come straight from the level planes and the sorted in-arcs (lvl_pred_kernel,
- * target-major like pred_cols*_kernel's output), so no essential-arc lists, slab transpose or
- * predecessor search over the distances; then the same row transposes and path-order reliability
- * passes as below. */
-static int dense_post_levels(int32_t n, int32_t ld, int32_t row0, int32_t nrows, uint32_t* d,
-                             double* rel, hipStream_t st, srt_build_stats* stats, dense_ws* ws,
-                             int lrows);
-
-static int dense_post(int32_t n, int32_t ld, int32_t row0, int32_t nrows, int32_t directed,
-                      const uint32_t* w, const double* r, uint32_t* d, const uint16_t* d16,
-                      double* rel, hipStream_t st, srt_build_stats* stats, ess_gather_fn gather,
-                      void* gctx, int lvl = 0) {
+/* One dense build: a whole matrix on one GPU (comm NULL: R = 1, rows [0, ld)) or the row shard
+ * [row0, row0 + nrows) of rank `me` of R. lrows: the shard's real (non-padding) rows. */
+struct dense_build {
+    const srt_comm* comm;
+    int R, me;
+    int32_t n, ld, row0, nrows, lrows, directed;
+    const uint32_t* w;
+    const double* r;
+    uint32_t* lat;
+    double* rel;
+    hipStream_t st;
+    srt_build_stats* stats; /* may be NULL */
+    evpool_t* evp;          /* stats->time_kernels */
     dense_ws* ws;
-    int rc = ws_get(&ws, n);
-    if (rc) return rc;
-    const int lrows = max(0, min(nrows, n - row0)); /* real (non-padding) local rows */
-    ws->pred16 = 0;
-    if (lvl) /* the distances came from the Dial levels: predecessors from the level planes */
-        return dense_post_levels(n, ld, row0, nrows, d, rel, st, stats, ws, lrows);
+};
+
+/* What the post pass of one build decided, for the steps after it (dense_finish_rows,
+ * dense_path_ms). */
+struct post_state {
+    int pred_layout = SRT_LVL_PRED_I32; /* the predecessor rows in ws->dt, a srt_lvl_pred_layout:
+                                         * I32, I16 (a level build, n <= 32768) or PK_COLS (a level
+                                         * build's packed words: the predecessor is their low half) */
+    int diag_done = 0;          /* the level post pass applied the diagonal rule itself */
+    int pn_cap = 0;             /* it took lvl_pred_near_kernel with this bucket capacity */
+    bool kev_on = false;        /* ws->kev bracket its predecessor and reliability kernels */
+    bool total_pending = false; /* the essential-arc total is on its way to ws->h_total */
+};
+
+/* the in-arcs of every target t: positions [ptr[t], ptr[t + 1]) of the tails col, latencies w and
+ * reliabilities r; `total` of them (small one-GPU builds: an upper bound, the count itself in the
+ * device word dtotal) */
+struct inarcs {
+    const int32_t *ptr, *col;
+    const uint32_t* w;
+    const double* r;
+    int32_t total;
+    const int32_t* dtotal;
+};
+
+/* The essential arcs of the local rows as lists per tail (made global by the gather hook of a
+ * sharded build), which for an undirected graph are the in-arc lists too. */
+static int ess_lists(const dense_build& b, const uint16_t* d16, ess_gather_fn gather, void* gctx,
+                     inarcs* out) {
+    dense_ws* ws = b.ws;
+    const int n = b.n, ld = b.ld, row0 = b.row0, lrows = b.lrows;
+    hipStream_t st = b.st;
+    int rc;
     SRT_HIPCHK(hipMemsetAsync(ws->cnt, 0, (size_t)(n + 1) * sizeof(int32_t), st));
     /* the exact u16 FW matrix when the build kept one: the same values in half the bytes
      * (C4: count 1.37 -> 1.08 ms, fill 1.52 -> 1.50 ms against the u32 table) */
-    const bool ess16 = d16 != nullptr;
-    if (lrows > 0 && ess16)
-        ess_count_kernel<uint16_t><<<lrows, 256, 0, st>>>(n, ld, row0, w, d16, ws->cnt);
+    if (lrows > 0 && d16)
+        ess_count_kernel<uint16_t><<<lrows, 256, 0, st>>>(n, ld, row0, b.w, d16, ws->cnt);
     else if (lrows > 0)
-        ess_count_kernel<uint32_t><<<lrows, 256, 0, st>>>(n, ld, row0, w, d, ws->cnt);
+        ess_count_kernel<uint32_t><<<lrows, 256, 0, st>>>(n, ld, row0, b.w, b.lat, ws->cnt);
     if (gather && (rc = gather(gctx, ws, n, 0, 0, st))) return rc; /* all-reduce counts */
     scan_kernel<<<1, 1024, 0, st>>>(n, ws->cnt, ws->ptr);
     SRT_HIPCHK(hipGetLastError());
     /* small graphs (n <= 2,048, one GPU) size the arc arrays for n (n - 1) arcs and let the
      * kernels read the total on the device: no host round trip in the middle of the pass */
     const bool nowait = !gather && n <= 2048;
-    const int32_t* dtotal = nowait ? ws->ptr + n : nullptr;
     int32_t total = 0;
     if (nowait) {
         total = n * (n - 1);
@@ -2069,159 +2087,191 @@ static int dense_post(int32_t n, int32_t ld, int32_t row0, int32_t nrows, int32_
         srt_set_error("essential-arc count overflow");
         return SRT_E_RANGE;
     }
-    if ((rc = grow_arcs(ws, (size_t)total + 1))) return rc;
-    if (lrows > 0) {
-        if (ess16)
-            ess_fill_kernel<uint16_t><<<lrows, 256, 0, st>>>(n, ld, row0, w, r, d16, ws->ptr,
-                                                             ws->col, ws->aw, ws->ar);
-        else
-            ess_fill_kernel<uint32_t><<<lrows, 256, 0, st>>>(n, ld, row0, w, r, d, ws->ptr,
-                                                             ws->col, ws->aw, ws->ar);
-    }
+    const size_t arcs = (size_t)total + 1;
+    if ((rc = ws->col.need(arcs)) || (rc = ws->aw.need(arcs)) || (rc = ws->ar.need(arcs))) return rc;
+    if (lrows > 0 && d16)
+        ess_fill_kernel<uint16_t><<<lrows, 256, 0, st>>>(n, ld, row0, b.w, b.r, d16, ws->ptr,
+                                                         ws->col.p, ws->aw.p, ws->ar.p);
+    else if (lrows > 0)
+        ess_fill_kernel<uint32_t><<<lrows, 256, 0, st>>>(n, ld, row0, b.w, b.r, b.lat, ws->ptr,
+                                                         ws->col.p, ws->aw.p, ws->ar.p);
     SRT_HIPCHK(hipGetLastError());
     if (gather && (rc = gather(gctx, ws, n, 1, total, st))) return rc; /* share the arcs */
-    const int32_t *iptr = ws->ptr, *icol = ws->col;
-    const uint32_t* iw = ws->aw;
-    const double* ir = ws->ar;
-    if (directed) {
-        size_t t1 = ws->tarc_cap, t2 = ws->tarc_cap, t3 = ws->tarc_cap;
-        if ((rc = ws_grow((void**)&ws->tcol, &t1, (size_t)total + 1, sizeof(int32_t)))) return rc;
-        if ((rc = ws_grow((void**)&ws->tw, &t2, (size_t)total + 1, sizeof(uint32_t)))) return rc;
-        if ((rc = ws_grow((void**)&ws->tr, &t3, (size_t)total + 1, sizeof(double)))) return rc;
-        ws->tarc_cap = t1;
-        SRT_HIPCHK(hipMemsetAsync(ws->cnt, 0, (size_t)n * sizeof(int32_t), st));
-        if (total > 0)
-            arc_count_by_col<<<min(srt_ceil_div(total, 256), 2048), 256, 0, st>>>(total, ws->col,
-                                                                                  ws->cnt, dtotal);
-        scan_kernel<<<1, 1024, 0, st>>>(n, ws->cnt, ws->tptr);
-        SRT_HIPCHK(hipMemcpyAsync(ws->cursor, ws->tptr, (size_t)n * sizeof(int32_t),
-                                  hipMemcpyDeviceToDevice, st));
-        arc_transpose_fill<<<srt_ceil_div(n, 256), 256, 0, st>>>(n, ws->ptr, ws->col, ws->aw, ws->ar,
-                                                                ws->cursor, ws->tcol, ws->tw, ws->tr);
-        SRT_HIPCHK(hipGetLastError());
-        iptr = ws->tptr;
-        icol = ws->tcol;
-        iw = ws->tw;
-        ir = ws->tr;
+    *out = {ws->ptr, ws->col.p, ws->aw.p, ws->ar.p, total, nowait ? ws->ptr + n : nullptr};
+    return SRT_OK;
+}
+
+/* The total of ess_lists into the stats, after the post pass's launches: known already, or (no
+ * round trip was made for it) copied to pinned memory for dense_finish_rows to read after the
+ * build's final wait. */
+static int ess_total(const dense_build& b, const inarcs& ess, post_state* ps) {
+    dense_ws* ws = b.ws;
+    if (!b.stats) return SRT_OK;
+    if (!ess.dtotal) {
+        b.stats->ess_arcs = ess.total;
+        return SRT_OK;
     }
-    SRT_HIPCHK(hipMemsetAsync(ws->depth, 0, sizeof(int32_t), st));
-    const bool ties = stats && stats->count_ties;
-    if (ties) SRT_HIPCHK(hipMemsetAsync(ws->ties, 0, sizeof(unsigned long long), st));
-    if (n > srt_dense_max_n()) { /* the entry points refuse such n before FW */
-        srt_set_error("dense predecessor pass supports n <= %d (n = %d)", srt_dense_max_n(), n);
-        return SRT_E_RANGE;
+    if (!ws->h_total) SRT_HIPCHK(hipHostMalloc((void**)&ws->h_total, sizeof(int32_t)));
+    SRT_HIPCHK(hipMemcpyAsync(ws->h_total, ess.dtotal, sizeof(int32_t), hipMemcpyDeviceToHost, b.st));
+    ps->total_pending = true;
+    return SRT_OK;
+}
+
+/* a directed graph's in-arcs: the essential lists (by tail) transposed into lists by head */
+static int inarcs_transpose(const dense_build& b, inarcs* in) {
+    dense_ws* ws = b.ws;
+    const int n = b.n, total = in->total;
+    hipStream_t st = b.st;
+    int rc;
+    const size_t arcs = (size_t)total + 1;
+    if ((rc = ws->tcol.need(arcs)) || (rc = ws->tw.need(arcs)) || (rc = ws->tr.need(arcs))) return rc;
+    SRT_HIPCHK(hipMemsetAsync(ws->cnt, 0, (size_t)n * sizeof(int32_t), st));
+    if (total > 0)
+        arc_count_by_col<<<min(srt_ceil_div(total, 256), 2048), 256, 0, st>>>(total, in->col, ws->cnt,
+                                                                              in->dtotal);
+    scan_kernel<<<1, 1024, 0, st>>>(n, ws->cnt, ws->tptr);
+    SRT_HIPCHK(hipMemcpyAsync(ws->cursor, ws->tptr, (size_t)n * sizeof(int32_t),
+                              hipMemcpyDeviceToDevice, st));
+    arc_transpose_fill<<<srt_ceil_div(n, 256), 256, 0, st>>>(n, in->ptr, in->col, in->w, in->r,
+                                                            ws->cursor, ws->tcol.p, ws->tw.p, ws->tr.p);
+    SRT_HIPCHK(hipGetLastError());
+    in->ptr = ws->tptr;
+    in->col = ws->tcol.p;
+    in->w = ws->tw.p;
+    in->r = ws->tr.p;
+    return SRT_OK;
+}
+
+/* the block-major transpose of the local rows `src` (64 sources per block) into ws->dt, then
+ * pred_cols_kernel over it */
+template <typename T>
+static void pred_cols_launch(const dense_build& b, const T* src, const inarcs& in, bool ties) {
+    dense_ws* ws = b.ws;
+    const int n = b.n, ld = b.ld, nrows = b.nrows;
+    /* the transpose is block-major (DT[s / 64][u][s % 64]): a 64-source block's slab is
+     * contiguous, so it spreads over every L2 set and fills whole lines (a row-major transpose
+     * with its power-of-two stride put the slab in a few sets: 37.6 vs 30.0 ms with one line
+     * of padding on C4) */
+    const size_t bsD = (size_t)ld * 64;
+    const int nsb = nrows / 64;
+    const int tch = max(1, min(n, 256));
+    const int tper = srt_ceil_div(n, tch);
+    const int grid = srt_ceil_div(nsb, 8) * 8 * tch;
+    T* dt = reinterpret_cast<T*>(ws->dt.p);
+    transpose_kernel<T, T, 64><<<dim3(srt_ceil_div(ld, 64), srt_ceil_div(nrows, 64)), 256, 0, b.st>>>(
+        nrows, ld, src, (size_t)ld, dt, bsD);
+    const auto kernel = ties ? pred_cols_kernel<T, true> : pred_cols_kernel<T, false>;
+    kernel<<<grid, 256, 0, b.st>>>(n, b.row0, b.lrows, nrows, bsD, dt, in.ptr, ws->uw.p, in.r,
+                                   ws->predt.p, ws->rt.p, nsb, tch, tper, !b.directed, ws->ties);
+}
+
+/* The predecessor search: DT[u][sl] = D[row0 + sl][u] into ws->dt, from the u16 working matrix
+ * when the build kept one (half the bytes per candidate arc: the search is bound by these reads),
+ * then the kernel for the distance width. It writes the predecessors and the reliabilities of
+ * their arcs target-major (ws->predt, ws->rt). */
+static int pred_search(const dense_build& b, const uint16_t* d16, const inarcs& in, bool ties) {
+    dense_ws* ws = b.ws;
+    const int n = b.n, ld = b.ld, nrows = b.nrows;
+    hipStream_t st = b.st;
+    int rc;
+    const size_t slab = (size_t)ld * nrows;
+    if ((rc = ws->dt.need(slab)) || (rc = ws->predt.need(slab)) ||
+        (rc = ws->uw.need((size_t)in.total + 1)))
+        return rc;
+    /* every distance fits a byte: the transposed slab of a 64-source block is 2 MB and stays in
+     * its XCD's L2. Byte distances without the tie count take the one-minimum form
+     * (pred_cols3_kernel; C4 post pass 38.1 -> 36.3 ms against pred_cols2_kernel, which the tie
+     * count keeps) */
+    const bool bytes = d16 && srt_fw16_small();
+    const bool key3 = bytes && !ties && n <= 32768;
+    if (in.total > 0 && key3)
+        pack_uk_kernel<<<srt_ceil_div(n, 4), 256, 0, st>>>(n, in.ptr, in.col, in.w, !b.directed,
+                                                           ws->uw.p);
+    else if (in.total > 0)
+        pack_uw_kernel<<<min(srt_ceil_div(in.total, 256), 2048), 256, 0, st>>>(in.total, in.col, in.w,
+                                                                               ws->uw.p, in.dtotal);
+    if ((rc = ws->rt.need(slab))) return rc;
+    if (!bytes) {
+        if (d16)
+            pred_cols_launch<uint16_t>(b, d16, in, ties);
+        else
+            pred_cols_launch<uint32_t>(b, b.lat, in, ties);
+        return SRT_OK;
     }
-    if (lrows > 0) {
-        const size_t slab = (size_t)ld * nrows;
-        /* the transpose is block-major (DT[s / 64][u][s % 64]): a 64-source block's slab is
-         * contiguous, so it spreads over every L2 set and fills whole lines (a row-major transpose
-         * with its power-of-two stride put the slab in a few sets: 37.6 vs 30.0 ms with one line
-         * of padding on C4) */
-        const size_t bsD = (size_t)ld * 64;
-        size_t c1 = ws->dt_cap, c2 = ws->predt_cap, c3 = ws->uw_cap;
-        if ((rc = ws_grow((void**)&ws->dt, &c1, slab, sizeof(uint32_t)))) return rc;
-        ws->dt_cap = c1;
-        if ((rc = ws_grow((void**)&ws->predt, &c2, slab, sizeof(int32_t)))) return rc;
-        ws->predt_cap = c2;
-        if ((rc = ws_grow((void**)&ws->uw, &c3, (size_t)total + 1, sizeof(uint2)))) return rc;
-        ws->uw_cap = c3;
-        /* byte distances without the tie count take the one-minimum form (pred_cols3_kernel;
-         * C4 post pass 38.1 -> 36.3 ms against pred_cols2_kernel, which the tie count keeps) */
-        const bool key3 = d16 && srt_fw16_small() && !ties && n <= 32768;
-        if (total > 0 && key3)
-            pack_uk_kernel<<<srt_ceil_div(n, 4), 256, 0, st>>>(n, iptr, icol, iw, !directed, ws->uw);
-        else if (total > 0)
-            pack_uw_kernel<<<min(srt_ceil_div(total, 256), 2048), 256, 0, st>>>(total, icol, iw,
-                                                                                ws->uw, dtotal);
-        /* DT[u][sl] = D[row0 + sl][u], from the u16 working matrix when the build kept one
-         * (half the bytes per candidate arc: the predecessor search is bound by these reads).
-         * With small distances (every local one <= 64 quanta) the search also emits the arc
-         * reliability and the reliability pass runs in level order in place; otherwise it emits
-         * arc indices for the sweep pass. */
-        const int nsb = nrows / 64;
-        const int tch = max(1, min(n, 256));
-        const int tper = srt_ceil_div(n, tch);
-        const int grid = srt_ceil_div(nsb, 8) * 8 * tch;
-        size_t c4 = ws->rt_cap;
-        if ((rc = ws_grow((void**)&ws->rt, &c4, slab, sizeof(double)))) return rc;
-        ws->rt_cap = c4;
-        if (d16 && srt_fw16_small()) {
-            /* every distance fits a byte: the transposed slab of a 64-source block is 2 MB and
-             * stays in its XCD's L2 */
-            uint8_t* dt8 = reinterpret_cast<uint8_t*>(ws->dt);
-            const int nsb2 = srt_ceil_div(nrows, 128);
-            transpose_kernel<uint16_t, uint8_t, 128><<<dim3(srt_ceil_div(ld, 64), srt_ceil_div(nrows, 64)),
-                                                     256, 0, st>>>(nrows, ld, d16, (size_t)ld, dt8,
-                                                                   (size_t)ld * 128);
-            /* 16 candidate arcs in flight per step: 17.3 ms on C4 against 18.7 (8) and 20.0 (32);
-             * streaming (non-temporal) output stores: 13.9 against 14.5 ms on C4, post pass 35.4
-             * against 36.3 ms, same box */
-            if (key3)
-                pred_cols3_kernel<16, true><<<srt_ceil_div(nsb2, 8) * 8 * tch, 256, 0, st>>>(
-                    n, row0, lrows, nrows, (size_t)ld * 128, dt8, iptr, ws->uw, ir, ws->predt, ws->rt,
-                    nsb2, tch, tper, !directed);
-            else if (ties)
-                pred_cols2_kernel<16, true><<<srt_ceil_div(nsb2, 8) * 8 * tch, 256, 0, st>>>(
-                    n, row0, lrows, nrows, (size_t)ld * 128, dt8, iptr, ws->uw, ir, ws->predt, ws->rt,
-                    nsb2, tch, tper, !directed, ws->ties);
-            else
-                pred_cols2_kernel<16, false><<<srt_ceil_div(nsb2, 8) * 8 * tch, 256, 0, st>>>(
-                    n, row0, lrows, nrows, (size_t)ld * 128, dt8, iptr, ws->uw, ir, ws->predt, ws->rt,
-                    nsb2, tch, tper, !directed, ws->ties);
-        } else if (d16) {
-            uint16_t* dt16 = reinterpret_cast<uint16_t*>(ws->dt);
-            transpose_kernel<uint16_t, uint16_t, 64><<<dim3(srt_ceil_div(ld, 64), srt_ceil_div(nrows, 64)),
-                                                         256, 0, st>>>(nrows, ld, d16, (size_t)ld, dt16, bsD);
-            if (ties)
-                pred_cols_kernel<uint16_t, true, true><<<grid, 256, 0, st>>>(
-                    n, row0, lrows, nrows, bsD, dt16, iptr, ws->uw, ir, ws->predt, ws->rt, nsb, tch,
-                    tper, !directed, ws->ties);
-            else
-                pred_cols_kernel<uint16_t, true, false><<<grid, 256, 0, st>>>(
-                    n, row0, lrows, nrows, bsD, dt16, iptr, ws->uw, ir, ws->predt, ws->rt, nsb, tch,
-                    tper, !directed, ws->ties);
-        } else {
-            transpose_kernel<uint32_t, uint32_t, 64><<<dim3(srt_ceil_div(ld, 64), srt_ceil_div(nrows, 64)),
-                                                         256, 0, st>>>(nrows, ld, d, (size_t)ld, ws->dt, bsD);
-            if (ties)
-                pred_cols_kernel<uint32_t, true, true><<<grid, 256, 0, st>>>(
-                    n, row0, lrows, nrows, bsD, ws->dt, iptr, ws->uw, ir, ws->predt, ws->rt, nsb, tch,
-                    tper, !directed, ws->ties);
-            else
-                pred_cols_kernel<uint32_t, true, false><<<grid, 256, 0, st>>>(
-                    n, row0, lrows, nrows, bsD, ws->dt, iptr, ws->uw, ir, ws->predt, ws->rt, nsb, tch,
-                    tper, !directed, ws->ties);
-        }
-        /* predecessor rows pred[sl][t] = predT[t][sl] (reuses the DT buffer) and the arc
-         * reliabilities straight into the rel rows, where the passes below finish them in place */
-        int32_t* pred = reinterpret_cast<int32_t*>(ws->dt);
-        /* (streaming stores measured neutral here: these transposes already run at ~5.3 TB/s) */
-        transpose_kernel<uint32_t><<<dim3(srt_ceil_div(nrows, 64), srt_ceil_div(n, 64)), 256, 0, st>>>(
-            n, nrows, reinterpret_cast<const uint32_t*>(ws->predt), (size_t)nrows,
-            reinterpret_cast<uint32_t*>(pred), (size_t)ld);
-        transpose_kernel<double><<<dim3(srt_ceil_div(nrows, 64), srt_ceil_div(n, 64)), 256, 0, st>>>(
-            n, nrows, ws->rt, (size_t)nrows, rel, (size_t)ld);
-        /* level order for rows whose distances span <= 64 quanta, sweeps for the rest
-         * (ws->cursor is free here and carries the per-row hand-over flags) */
-        /* the target-major predecessors (predt) are free after the transpose: the order kernel's
-         * per-row lists */
-        if ((rc = rel_rows_launch(n, ld, row0, lrows, d, pred, rel, ws->depth, ws->cursor, nullptr,
-                                  st, nullptr, nullptr, nullptr, nullptr, 0,
-                                  reinterpret_cast<uint32_t*>(ws->predt))))
-            return rc;
-    }
-    if (stats && nowait) { /* read after the build's final wait (dense_collect_total) */
-        if (!ws->h_total) SRT_HIPCHK(hipHostMalloc((void**)&ws->h_total, sizeof(int32_t)));
-        SRT_HIPCHK(hipMemcpyAsync(ws->h_total, ws->ptr + n, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        ws->total_pending = 1;
-    } else if (stats) {
-        stats->ess_arcs = total;
+    uint8_t* dt8 = reinterpret_cast<uint8_t*>(ws->dt.p);
+    const size_t bsD = (size_t)ld * 128;
+    const int nsb = srt_ceil_div(nrows, 128);
+    const int tch = max(1, min(n, 256));
+    const int tper = srt_ceil_div(n, tch);
+    const int grid = srt_ceil_div(nsb, 8) * 8 * tch;
+    transpose_kernel<uint16_t, uint8_t, 128><<<dim3(srt_ceil_div(ld, 64), srt_ceil_div(nrows, 64)), 256,
+                                             0, st>>>(nrows, ld, d16, (size_t)ld, dt8, bsD);
+    /* 16 candidate arcs in flight per step: 17.3 ms on C4 against 18.7 (8) and 20.0 (32);
+     * streaming (non-temporal) output stores: 13.9 against 14.5 ms on C4, post pass 35.4
+     * against 36.3 ms, same box */
+    if (key3) {
+        pred_cols3_kernel<<<grid, 256, 0, st>>>(n, b.row0, b.lrows, nrows, bsD, dt8, in.ptr, ws->uw.p,
+                                                in.r, ws->predt.p, ws->rt.p, nsb, tch, tper,
+                                                !b.directed);
+    } else {
+        const auto kernel = ties ? pred_cols2_kernel<true> : pred_cols2_kernel<false>;
+        kernel<<<grid, 256, 0, st>>>(n, b.row0, b.lrows, nrows, bsD, dt8, in.ptr, ws->uw.p, in.r,
+                                     ws->predt.p, ws->rt.p, nsb, tch, tper, !b.directed, ws->ties);
     }
     return SRT_OK;
 }
 
-/* The post pass of a held level build: its predecessors (srt_levels_pred) into source-major rows in
- * ws->dt, then the reliability pass over them, in the form the build was made for.
+/* predecessor rows pred[sl][t] = predT[t][sl] (reuses the DT buffer) and the arc reliabilities
+ * straight into the rel rows, where the reliability passes finish them in place
+ * (streaming stores measured neutral here: these transposes already run at ~5.3 TB/s) */
+static void pred_rows(const dense_build& b) {
+    dense_ws* ws = b.ws;
+    const dim3 grid(srt_ceil_div(b.nrows, 64), srt_ceil_div(b.n, 64));
+    transpose_kernel<uint32_t><<<grid, 256, 0, b.st>>>(
+        b.n, b.nrows, reinterpret_cast<const uint32_t*>(ws->predt.p), (size_t)b.nrows, ws->dt.p,
+        (size_t)b.ld);
+    transpose_kernel<double><<<grid, 256, 0, b.st>>>(b.n, b.nrows, ws->rt.p, (size_t)b.nrows, b.rel,
+                                                     (size_t)b.ld);
+}
+
+/* The post pass of a Floyd-Warshall build (d16: its exact u16 matrix, or NULL): the essential-arc
+ * lists, the canonical predecessor of every pair from them, and the path-order reliabilities. With
+ * small distances (every local one <= 64 quanta) the reliability pass runs in level order in
+ * place; the sweeps take the rest. */
+static int dense_post(const dense_build& b, const uint16_t* d16, ess_gather_fn gather, void* gctx,
+                      post_state* ps) {
+    dense_ws* ws = b.ws;
+    hipStream_t st = b.st;
+    int rc;
+    inarcs ess, in;
+    if ((rc = ess_lists(b, d16, gather, gctx, &ess))) return rc;
+    in = ess;
+    if (b.directed && (rc = inarcs_transpose(b, &in))) return rc;
+    SRT_HIPCHK(hipMemsetAsync(ws->depth, 0, sizeof(int32_t), st));
+    const bool ties = b.stats && b.stats->count_ties;
+    if (ties) SRT_HIPCHK(hipMemsetAsync(ws->ties, 0, sizeof(unsigned long long), st));
+    if (b.n > srt_dense_max_n()) { /* the entry points refuse such n before FW */
+        srt_set_error("dense predecessor pass supports n <= %d (n = %d)", srt_dense_max_n(), b.n);
+        return SRT_E_RANGE;
+    }
+    if (b.lrows > 0) {
+        if ((rc = pred_search(b, d16, in, ties))) return rc;
+        pred_rows(b);
+        /* ws->cursor is free here and carries the per-row hand-over flags; the target-major
+         * predecessors (predt) are free after the transpose: the order kernel's per-row lists */
+        if ((rc = rel_fw_rows(b.n, b.ld, b.row0, b.lrows, b.lat, reinterpret_cast<int32_t*>(ws->dt.p),
+                              b.rel, ws->depth, ws->cursor, reinterpret_cast<uint32_t*>(ws->predt.p),
+                              st)))
+            return rc;
+    }
+    return ess_total(b, ess, ps);
+}
+
+/* The post pass of a held level build (levels.hip): the canonical predecessors and their arc
+ * reliabilities come straight from the level planes and the sorted in-arcs (srt_levels_pred,
+ * target-major like pred_cols*_kernel's output), so no essential-arc lists, slab transpose or
+ * predecessor search over the distances; they go into source-major rows in ws->dt, then the
+ * reliability pass runs over them, in the form the build was made for.
  * Packed (SRT_LVL_POST_PK_*): one word per pair with the level, then rel_pk_kernel, which writes
  * the u32 rows too: no u8 rows, no f64 slab. The words come straight from lvl_pred_rows_kernel (no
  * predt slab, no transpose); with the tie count, or under SRT_FORM pkw=2, target-major from
@@ -2230,9 +2280,13 @@ static int dense_post(int32_t n, int32_t ld, int32_t row0, int32_t nrows, int32_
  * widened by the transpose into the int32 rows the reliability passes read; with the build's table
  * of distinct arc reliabilities, one packed word per pair (predecessor | index << 16): 4 B written,
  * transposed and read instead of 2 + 8. */
-static int dense_post_levels(int32_t n, int32_t ld, int32_t row0, int32_t nrows, uint32_t* d,
-                             double* rel, hipStream_t st, srt_build_stats* stats, dense_ws* ws,
-                             int lrows) {
+static int dense_post_levels(const dense_build& b, post_state* ps) {
+    dense_ws* ws = b.ws;
+    const int n = b.n, ld = b.ld, row0 = b.row0, nrows = b.nrows, lrows = b.lrows;
+    uint32_t* d = b.lat;
+    double* rel = b.rel;
+    hipStream_t st = b.st;
+    srt_build_stats* stats = b.stats;
     int rc;
     const srt_lvl_post_form form = srt_levels_pkw_ready();
     const bool packed = form != SRT_LVL_POST_U8;
@@ -2255,110 +2309,107 @@ static int dense_post_levels(int32_t n, int32_t ld, int32_t row0, int32_t nrows,
                                                      : SRT_LVL_PRED_I32;
         const bool rows = out == SRT_LVL_PRED_PK_ROWS, pkw = out == SRT_LVL_PRED_PK_COLS || rows;
         const size_t slab = (size_t)ld * nrows;
-        size_t c1 = ws->dt_cap, c2 = ws->predt_cap, c4 = ws->rt_cap;
-        if ((rc = ws_grow((void**)&ws->dt, &c1, slab, sizeof(uint32_t)))) return rc;
-        ws->dt_cap = c1;
-        if (!rows && (rc = ws_grow((void**)&ws->predt, &c2, slab, sizeof(int32_t)))) return rc;
-        ws->predt_cap = c2;
-        if (!packed && (rc = ws_grow((void**)&ws->rt, &c4, slab, sizeof(double)))) return rc;
-        ws->rt_cap = c4;
+        if ((rc = ws->dt.need(slab))) return rc;
+        if (!rows && (rc = ws->predt.need(slab))) return rc;
+        if (!packed && (rc = ws->rt.need(slab))) return rc;
         if (ties) SRT_HIPCHK(hipMemsetAsync(ws->ties, 0, sizeof(unsigned long long), st));
         const bool kt = stats && stats->time_kernels;
         if (kt && !ws->kev[0])
             for (int i = 0; i < 4; i++) SRT_HIPCHK(hipEventCreate(&ws->kev[i]));
         if (kt) SRT_HIPCHK(hipEventRecord(ws->kev[0], st));
         SRT_HIPCHK(hipMemsetAsync(ws->depth + 1, 0, sizeof(int32_t), st));
-        if ((rc = srt_levels_pred(rows ? (void*)ws->dt : (void*)ws->predt, out, packed ? nullptr : ws->rt,
-                                  rows ? (size_t)ld : (size_t)nrows, ties ? ws->ties : NULL, ws->depth + 1,
-                                  &ws->pn_cap, st)))
+        if ((rc = srt_levels_pred(rows ? (void*)ws->dt.p : (void*)ws->predt.p, out,
+                                  packed ? nullptr : ws->rt.p, rows ? (size_t)ld : (size_t)nrows,
+                                  ties ? ws->ties : NULL, ws->depth + 1, &ps->pn_cap, st)))
             return rc;
         if (kt) SRT_HIPCHK(hipEventRecord(ws->kev[1], st));
         /* the target-major slabs into rows of ws->dt (int16 rows: the reliability passes read them
          * as they are) and of rel */
         const dim3 tgrid(srt_ceil_div(nrows, 64), srt_ceil_div(n, 64));
         if (out == SRT_LVL_PRED_I16)
-            transpose_kernel<int16_t><<<tgrid, 256, 0, st>>>(n, nrows, reinterpret_cast<const int16_t*>(ws->predt),
-                                                             (size_t)nrows, reinterpret_cast<int16_t*>(ws->dt),
+            transpose_kernel<int16_t><<<tgrid, 256, 0, st>>>(n, nrows, reinterpret_cast<const int16_t*>(ws->predt.p),
+                                                             (size_t)nrows, reinterpret_cast<int16_t*>(ws->dt.p),
                                                              (size_t)ld);
         else if (!rows)
-            transpose_kernel<uint32_t><<<tgrid, 256, 0, st>>>(n, nrows, reinterpret_cast<const uint32_t*>(ws->predt),
-                                                              (size_t)nrows, reinterpret_cast<uint32_t*>(ws->dt),
-                                                              (size_t)ld);
-        if (!pkw) transpose_kernel<double><<<tgrid, 256, 0, st>>>(n, nrows, ws->rt, (size_t)nrows, rel, (size_t)ld);
+            transpose_kernel<uint32_t><<<tgrid, 256, 0, st>>>(n, nrows, reinterpret_cast<const uint32_t*>(ws->predt.p),
+                                                              (size_t)nrows, ws->dt.p, (size_t)ld);
+        if (!pkw) transpose_kernel<double><<<tgrid, 256, 0, st>>>(n, nrows, ws->rt.p, (size_t)nrows, rel, (size_t)ld);
         /* what ws->dt holds for dense_path_ms: int32, int16, or packed words (their low half) */
-        ws->pred16 = pkw ? (int)SRT_LVL_PRED_PK_COLS : (int)out;
+        ps->pred_layout = pkw ? (int)SRT_LVL_PRED_PK_COLS : (int)out;
         SRT_HIPCHK(hipMemsetAsync(ws->depth, 0, sizeof(int32_t), st));
         if (kt) SRT_HIPCHK(hipEventRecord(ws->kev[2], st));
+        /* u8 rows: every level-built distance is <= 254 quanta, level order in place for every row
+         * that spans <= 64 quanta, sweeps for the rest (as dense_post) */
         if (packed)
-            rc = rel_pk_launch(n, ld, row0, lrows, reinterpret_cast<uint32_t*>(ws->dt), d, rel, rtab, ntab,
-                               ws->depth, ws->cursor, st);
-        else /* every level-built distance is <= 254 quanta: level order in place for every row that
-              * spans <= 64 quanta, sweeps for the rest (as dense_post); the level rows as u8 */
-            rc = rel_rows_launch(n, ld, row0, lrows, d, reinterpret_cast<int32_t*>(ws->dt), rel, ws->depth,
-                                 ws->cursor, nullptr, st, srt_levels_l8(),
-                                 out == SRT_LVL_PRED_I16 ? reinterpret_cast<int16_t*>(ws->dt) : nullptr,
-                                 pkw ? reinterpret_cast<uint32_t*>(ws->dt) : nullptr, rtab, ntab);
+            rc = rel_pk_launch(n, ld, row0, lrows, ws->dt.p, d, rel, rtab, ntab, ws->depth, ws->cursor, st);
+        else if (pkw)
+            rc = rel_level_rows(n, ld, row0, lrows, d, srt_levels_l8(), ws->dt.p, rel, ws->depth,
+                                ws->cursor, rtab, ntab, st);
+        else if (out == SRT_LVL_PRED_I16)
+            rc = rel_level_rows(n, ld, row0, lrows, d, srt_levels_l8(), reinterpret_cast<int16_t*>(ws->dt.p),
+                                rel, ws->depth, ws->cursor, nullptr, 0, st);
+        else
+            rc = rel_level_rows(n, ld, row0, lrows, d, srt_levels_l8(), reinterpret_cast<int32_t*>(ws->dt.p),
+                                rel, ws->depth, ws->cursor, nullptr, 0, st);
         if (rc) return rc;
         if (kt) {
             SRT_HIPCHK(hipEventRecord(ws->kev[3], st));
-            ws->kev_on = 1;
+            ps->kev_on = true;
         }
         /* the diagonal rule from the keys the level build's count pass took (no second read of the
          * w rows); directed builds keep dense_diag_kernel */
-        if ((rc = srt_levels_diag(n, ld, d, rel, st, &ws->diag_done))) return rc;
+        if ((rc = srt_levels_diag(n, ld, d, rel, st, &ps->diag_done))) return rc;
     }
     srt_levels_release(st);
     if (stats) stats->ess_arcs = 0; /* no essential-arc lists in this form */
     return SRT_OK;
 }
 
-/* the essential-arc total of a post pass that did not wait for it (after the stream's work) */
-static void dense_collect_total(int32_t n, srt_build_stats* stats) {
-    dense_ws* ws;
-    if (!stats || ws_get(&ws, n) || !ws->total_pending) return;
-    stats->ess_arcs = *ws->h_total;
-    ws->total_pending = 0;
-}
-
-static int dense_finish_rows(int32_t n, int32_t ld, int32_t row0, int32_t nrows, const uint32_t* w,
-                             const double* r, uint32_t* d, double* rel, hipStream_t st,
-                             srt_build_stats* stats) {
-    const int lrows = max(0, min(nrows, n - row0));
-    dense_ws* wsd;
-    int rcw = ws_get(&wsd, n);
-    if (rcw) return rcw;
-    if (lrows > 0 && !wsd->diag_done)
-        dense_diag_kernel<<<srt_ceil_div(lrows, 4), 256, 0, st>>>(n, ld, row0, lrows, w, r, d, rel);
-    wsd->diag_done = 0;
+/* The diagonal rule where the post pass left it, then (stats) the build's first wait: what the post
+ * pass counted on the device, its deferred essential-arc total and its kernel events. */
+static int dense_finish_rows(const dense_build& b, const post_state& ps) {
+    dense_ws* ws = b.ws;
+    hipStream_t st = b.st;
+    srt_build_stats* stats = b.stats;
+    if (b.lrows > 0 && !ps.diag_done)
+        dense_diag_kernel<<<srt_ceil_div(b.lrows, 4), 256, 0, st>>>(b.n, b.ld, b.row0, b.lrows, b.w, b.r,
+                                                                    b.lat, b.rel, nullptr);
     SRT_HIPCHK(hipGetLastError());
-    if (stats) {
-        dense_ws* ws;
-        int rc = ws_get(&ws, n);
-        if (rc) return rc;
-        int32_t depth[2] = {0, 0};
-        unsigned long long nt = 0;
-        SRT_HIPCHK(hipMemcpyAsync(depth, ws->depth, (ws->pn_cap ? 2 : 1) * sizeof(int32_t),
-                                  hipMemcpyDeviceToHost, st));
-        if (stats->count_ties)
-            SRT_HIPCHK(hipMemcpyAsync(&nt, ws->ties, sizeof(nt), hipMemcpyDeviceToHost, st));
-        SRT_HIPCHK(hipStreamSynchronize(st));
-        stats->max_depth = depth[0];
-        stats->tied_pairs = (int64_t)nt;
-        stats->pred_near = ws->pn_cap;
-        stats->pred_near_over = depth[1];
-        ws->pn_cap = 0;
-        dense_collect_total(n, stats);
-        if (ws->kev_on) {
-            float a = 0, b = 0;
-            SRT_HIPCHK(hipEventElapsedTime(&a, ws->kev[0], ws->kev[1]));
-            SRT_HIPCHK(hipEventElapsedTime(&b, ws->kev[2], ws->kev[3]));
-            stats->ms_pred = a;
-            stats->ms_rel = b;
-            ws->kev_on = 0;
-        }
+    if (!stats) return SRT_OK;
+    int32_t depth[2] = {0, 0};
+    unsigned long long nt = 0;
+    SRT_HIPCHK(hipMemcpyAsync(depth, ws->depth, (ps.pn_cap ? 2 : 1) * sizeof(int32_t),
+                              hipMemcpyDeviceToHost, st));
+    if (stats->count_ties)
+        SRT_HIPCHK(hipMemcpyAsync(&nt, ws->ties, sizeof(nt), hipMemcpyDeviceToHost, st));
+    SRT_HIPCHK(hipStreamSynchronize(st));
+    stats->max_depth = depth[0];
+    stats->tied_pairs = (int64_t)nt;
+    stats->pred_near = ps.pn_cap;
+    stats->pred_near_over = depth[1];
+    if (ps.total_pending) stats->ess_arcs = *ws->h_total;
+    if (ps.kev_on) {
+        float a = 0, c = 0;
+        SRT_HIPCHK(hipEventElapsedTime(&a, ws->kev[0], ws->kev[1]));
+        SRT_HIPCHK(hipEventElapsedTime(&c, ws->kev[2], ws->kev[3]));
+        stats->ms_pred = a;
+        stats->ms_rel = c;
     }
     return SRT_OK;
 }
+
+/* HIP events of one build, released on every return path */
+struct build_events {
+    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+    ~build_events() {
+        for (hipEvent_t x : e)
+            if (x) (void)hipEventDestroy(x);
+    }
+    int create() {
+        for (hipEvent_t& x : e) SRT_HIPCHK(hipEventCreate(&x));
+        return SRT_OK;
+    }
+};
 
 /* ---- a few source rows on a dense graph (srt_dense_rows_build_device) ---------------------- */
 /* The canonical predecessor of (source row i, target t) is argmin over u with
@@ -2533,16 +2584,9 @@ int srt_dense_rows_build_device(int32_t n, int32_t ld, int32_t nsub, const int32
     uint32_t* maxd = (uint32_t*)sc.p[5];
     int32_t* ccnt = (int32_t*)sc.p[5] + ld;
     int32_t* ptr = ccnt + ld + 1; /* n + 1 candidate offsets */
-    hipEvent_t e0, e1, e2;
-    SRT_HIPCHK(hipEventCreate(&e0));
-    SRT_HIPCHK(hipEventCreate(&e1));
-    SRT_HIPCHK(hipEventCreate(&e2));
-    struct evs {
-        hipEvent_t* e[3];
-        ~evs() {
-            for (hipEvent_t* x : e) (void)hipEventDestroy(*x);
-        }
-    } ev{{&e0, &e1, &e2}};
+    build_events ev;
+    if ((rc = ev.create())) return rc;
+    hipEvent_t e0 = ev.e[0], e1 = ev.e[1], e2 = ev.e[2];
     SRT_HIPCHK(hipEventRecord(e0, st));
     int exact = 0, small = 0, passes = 0;
     rc = srt_fw16_rows(n, ld, nsub, dverts, w, w16, ds, lat_rows, st, &exact, &small, &passes);
@@ -2580,7 +2624,18 @@ int srt_dense_rows_build_device(int32_t n, int32_t ld, int32_t nsub, const int32
         rows_pred_kernel<false><<<pg, 256, 0, st>>>(n, ld, nsub, dverts, dt, ptr, cand, r, pred,
                                                      rel_rows, ties);
     SRT_HIPCHK(hipGetLastError());
-    if ((rc = rel_rows_launch(n, ld, 0, nsub, lat_rows, pred, rel_rows, depth, sweep, dverts, st)))
+    /* the reliability pass over the listed sources: level order, then the sweeps (no deep or
+     * order pass: they take rows by index) */
+    if (rel_tree_on(n)) {
+        rel_tree_launch(n, ld, 0, nsub, lat_rows, (const int32_t*)pred, rel_rows, depth, sweep, dverts,
+                        st, nullptr, 0);
+        SRT_HIPCHK(hipGetLastError());
+    } else if ((rc = rel_levels_launch(n, ld, 0, nsub, lat_rows, pred, rel_rows, depth, sweep, dverts,
+                                       st))) {
+        return rc;
+    }
+    if ((rc = rel_sweeps_launch(n, ld, 0, nsub, (const int32_t*)pred, rel_rows, depth, sweep, dverts,
+                                st)))
         return rc;
     dense_diag_kernel<<<srt_ceil_div(nsub, 4), 256, 0, st>>>(n, ld, 0, nsub, w, r, lat_rows, rel_rows,
                                                              dverts);
@@ -2634,34 +2689,11 @@ extern "C" int srt_dense_rows_build(int32_t n, int32_t ld, int32_t nsub, const i
     return SRT_OK;
 }
 
-int srt_dense_post_device(int32_t n, int32_t ld, int32_t directed, const uint32_t* w, const double* r,
-                          uint32_t* d, const uint16_t* d16, double* rel, hipStream_t st,
-                          srt_build_stats* stats, int lvl) {
-    int rc = dense_post(n, ld, 0, ld, directed, w, r, d, d16, rel, st, stats, NULL, NULL, lvl);
-    if (rc) return rc;
-    return dense_finish_rows(n, ld, 0, ld, w, r, d, rel, st, stats);
-}
-
 /* ------------------------------------------------------------------------------------------ */
-/* public device-resident dense build                                                         */
+/* the dense build: one GPU, or a row shard over RCCL (one process per GPU)                   */
 /* ------------------------------------------------------------------------------------------ */
 extern "C" int srt_dense_max_n(void) { return SRT_DENSE_MAX_N; }
 
-/* HIP events of one build, released on every return path */
-struct build_events {
-    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-    ~build_events() {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-    int create() {
-        for (hipEvent_t& x : e) SRT_HIPCHK(hipEventCreate(&x));
-        return SRT_OK;
-    }
-};
-
-/* f64 path-order ms rows [row0, row0 + lrows) from the predecessor rows the post pass left in the
- * workspace (tables.hip); runs after the diagonal rule */
 template <typename T>
 __global__ void widen16_kernel(size_t cnt, const T* __restrict__ in, int32_t* __restrict__ out) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt;
@@ -2669,187 +2701,52 @@ __global__ void widen16_kernel(size_t cnt, const T* __restrict__ in, int32_t* __
         out[i] = (int16_t)(in[i] & 0xFFFF); /* int16 rows, or the packed words' low half */
 }
 
-static int dense_path_ms(int32_t n, int32_t ld, int32_t row0, int32_t nrows, const uint32_t* d,
-                         uint64_t q, double* lms, hipStream_t st) {
-    const int lrows = max(0, min(nrows, n - row0));
-    if (lrows == 0) return SRT_OK;
-    dense_ws* ws;
-    int rc = ws_get(&ws, n);
-    if (rc) return rc;
-    const int32_t* pred = reinterpret_cast<const int32_t*>(ws->dt);
-    if (ws->pred16) { /* the level post pass left int16 rows: widened into the free slab */
-        const size_t cnt = (size_t)lrows * ld;
+/* f64 path-order ms rows [row0, row0 + lrows) from the predecessor rows the post pass left in the
+ * workspace (tables.hip); runs after the diagonal rule */
+static int dense_path_ms(const dense_build& b, const post_state& ps, uint64_t q, double* lms) {
+    dense_ws* ws = b.ws;
+    if (b.lrows == 0) return SRT_OK;
+    int rc;
+    const int32_t* pred = reinterpret_cast<const int32_t*>(ws->dt.p);
+    if (ps.pred_layout != SRT_LVL_PRED_I32) { /* the level post pass left int16 rows or packed
+                                               * words: widened into the free slab */
+        const size_t cnt = (size_t)b.lrows * b.ld;
         /* (the source-major packed post pass keeps no predt slab: taken here, when asked for) */
-        size_t c2 = ws->predt_cap;
-        if ((rc = ws_grow((void**)&ws->predt, &c2, (size_t)nrows * ld, sizeof(int32_t)))) return rc;
-        ws->predt_cap = c2;
+        if ((rc = ws->predt.need((size_t)b.nrows * b.ld))) return rc;
         const int64_t nb = srt_ceil_div((int64_t)cnt, 256);
         const unsigned g = (unsigned)(nb < 65536 ? nb : 65536);
-        if (ws->pred16 == 2)
-            widen16_kernel<uint32_t><<<g, 256, 0, st>>>(cnt, reinterpret_cast<const uint32_t*>(ws->dt),
-                                                        ws->predt);
+        if (ps.pred_layout == SRT_LVL_PRED_PK_COLS)
+            widen16_kernel<uint32_t><<<g, 256, 0, b.st>>>(cnt, ws->dt.p, ws->predt.p);
         else
-            widen16_kernel<int16_t><<<g, 256, 0, st>>>(cnt, reinterpret_cast<const int16_t*>(ws->dt),
-                                                       ws->predt);
+            widen16_kernel<int16_t><<<g, 256, 0, b.st>>>(cnt, reinterpret_cast<const int16_t*>(ws->dt.p),
+                                                         ws->predt.p);
         SRT_HIPCHK(hipGetLastError());
-        pred = ws->predt;
+        pred = ws->predt.p;
     }
-    return srt_path_ms_rows(n, lrows, NULL, row0, d, (size_t)ld, pred, (size_t)ld, NULL, NULL, NULL, q,
-                            lms, (size_t)ld, st);
+    return srt_path_ms_rows(b.n, b.lrows, NULL, b.row0, b.lat, (size_t)b.ld, pred, (size_t)b.ld, NULL,
+                            NULL, NULL, q, lms, (size_t)b.ld, b.st);
 }
 
-/* Dial levels (levels.hip) instead of the FW when the graph's distances are small enough for the
- * level budget to beat the FW's predicted time (61 T relaxations/s, the measured update rate;
- * symmetric rounds do half the relaxations, plus the rounds' chain). n >= 4,096: below that the
- * FW's squaring or rounds
- * cost less than the levels' launches. SRT_FORM levels=0 keeps the FW, =1 tries the levels at any
- * size. *exact = 1 when the levels settled every pair (the u16 matrix and lat rows are final). */
-static int dense_try_levels(const srt_comm* comm, int n, int ld, int row0, int nrows, int directed,
-                            const uint32_t* w_rows, const double* r_rows, uint32_t* lat_rows,
-                            hipStream_t st,
-                            evpool_t* evp, srt_build_stats* stats, int* exact) {
-    *exact = 0;
-    const int mode = srt_form_int("levels", -1);
-    if (mode == 0 || (mode < 0 && n < 4096) || ld % 128) return SRT_OK;
-    /* relaxations at the update's rate + ~50 us of round chain per 128 pivots, for the largest
-     * shard (the same on every rank; srt_levels_build also agrees the budget by a min all-reduce) */
-    int max_rows = nrows;
-    const int R = comm ? srt_comm_size(comm) : 1;
-    for (int q = 0; q < R && R > 1; q++) {
-        int32_t qb = 0, qe = 0;
-        srt_shard_rows(ld, SRT_SHARD_ALIGN, R, q, &qb, &qe);
-        max_rows = max(max_rows, qe - qb);
-    }
-    const double fw_ms = (double)max_rows * ld * ld / (directed ? 1.0 : 2.0) / 6.1e10 + ld / 128 * 0.05;
-    if (evp) {
-        evp->used = 0;
-        evp->group = 2;
-    }
-    int nlev = 0;
-    int64_t bytes = 0;
-    const int rc = srt_fw16_levels(comm, n, ld, row0, nrows, directed, w_rows, r_rows, lat_rows, st, evp,
-                                   mode > 0 ? 1e30 : fw_ms, &nlev, &bytes);
-    if (rc) return rc;
-    if (stats) {
-        stats->levels = nlev;
-        stats->work_bytes = nlev ? bytes : 0;
-    }
-    *exact = nlev > 0;
-    return SRT_OK;
-}
-
-int srt_dense_build_device_ms(int32_t n, int32_t ld, int32_t directed, const uint32_t* w,
-                              const double* r, uint32_t* lat, double* rel, double* lat_ms,
-                              uint64_t quantum_ns, hipStream_t st, int32_t fw_block,
-                              srt_build_stats* stats) {
-    if (n <= 0 || ld < n || ld % B || !w || !r || !lat || !rel) {
-        srt_set_error("srt_dense_build_device: bad arguments (n=%d ld=%d)", n, ld);
-        return SRT_E_ARG;
-    }
-    if (n > srt_dense_max_n()) { /* refused before any FW round runs */
-        srt_set_error("dense build supports n <= %d (n = %d); use the sparse SSSP", srt_dense_max_n(), n);
-        return SRT_E_RANGE;
-    }
-    if (fw_block != 0 && fw_block != B) {
-        srt_set_error("srt_dense_build_device: fw_block must be 0 or %d", B);
-        return SRT_E_ARG;
-    }
-    build_events ev;
-    int rc = ev.create();
-    if (rc) return rc;
-    hipEvent_t e0 = ev.e[0], e1 = ev.e[1], e2 = ev.e[2];
-    SRT_HIPCHK(hipEventRecord(e0, st));
-    evpool_t* evp = NULL;
-    if (stats && stats->time_kernels && (rc = evpool_begin(&evp, ld / B))) return rc;
-    /* narrowest exact encoding first: Dial levels (small distances) -> f16-compare u16 -> pk_min
-     * u16 -> u32 */
-    int exact = 0, enc = SRT_DENC_U32;
-    if ((rc = dense_try_levels(NULL, n, ld, 0, ld, directed, w, r, lat, st, evp, stats, &exact)))
-        return rc;
-    if (exact) enc = SRT_DENC_LEVELS;
-    for (int fm = 1; fm >= 0 && !exact && ld % 128 == 0; --fm) {
-        if (evp) {
-            evp->used = 0;
-            evp->group = 2;
-        }
-        int fw_enc = SRT_DENC_U32;
-        rc = srt_fw16_build(n, ld, 0, ld, w, lat, st, evp, NULL, NULL, NULL, 0, fm, !directed,
-                            &fw_enc, &exact);
-        if (rc) return rc;
-        if (exact) enc = fw_enc;
-    }
-    if (!exact) { /* u32 path: ld not a multiple of 128, or a distance reached 0x7FFF quanta */
-        if (evp) {
-            evp->used = 0;
-            evp->group = 2;
-        }
-        dim3 g(srt_ceil_div(ld, 256), ld);
-        init_dist_kernel<<<g, 256, 0, st>>>(n, ld, 0, w, lat);
-        SRT_HIPCHK(hipGetLastError());
-        rc = srt_dense_fw_device(n, ld, lat, st, evp);
-        if (rc) return rc;
-    }
-    SRT_HIPCHK(hipEventRecord(e1, st));
-    rc = srt_dense_post_device(n, ld, directed, w, r, lat, exact ? srt_fw16_matrix() : NULL, rel,
-                               st, stats, enc == SRT_DENC_LEVELS);
-    if (rc) return rc;
-    if (lat_ms) {
-        if ((rc = dense_path_ms(n, ld, 0, ld, lat, quantum_ns, lat_ms, st))) return rc;
-    }
-    SRT_HIPCHK(hipEventRecord(e2, st));
-    if (stats) {
-        SRT_HIPCHK(hipEventSynchronize(e2));
-        float a = 0, b = 0;
-        SRT_HIPCHK(hipEventElapsedTime(&a, e0, e1));
-        SRT_HIPCHK(hipEventElapsedTime(&b, e1, e2));
-        stats->algo = SRT_ALGO_DENSE_FW;
-        stats->fw_block = B;
-        stats->dist_enc = enc;
-        stats->ms_fw = a;
-        stats->ms_post = b;
-        stats->ms_total = a + b;
-        if (evp && (rc = evpool_sum(evp, e2, stats))) return rc;
-    }
-    return SRT_OK;
-}
-
-extern "C" int srt_dense_build_device(int32_t n, int32_t ld, int32_t directed, const uint32_t* w,
-                                      const double* r, uint32_t* lat, double* rel, void* stream,
-                                      int32_t fw_block, srt_build_stats* stats) {
-    return srt_dense_build_device_ms(n, ld, directed, w, r, lat, rel, NULL, 0, (hipStream_t)stream,
-                                     fw_block, stats);
-}
-
-/* ------------------------------------------------------------------------------------------ */
-/* row-sharded dense build over RCCL (one process per GPU)                                    */
-/* ------------------------------------------------------------------------------------------ */
-/* collectives: srt_coll_* (comm.hip) -- RCCL, or virtual ranks sharing one device */
-
-typedef struct {
-    const srt_comm* comm;
-    int ld;
-} shard_ctx;
-
+/* the hooks of a sharded build (ctx: its dense_build); collectives: srt_coll_* (comm.hip) -- RCCL,
+ * or virtual ranks sharing one device */
 static int shard_owner(void* vctx, int k0) {
-    const shard_ctx* ctx = (const shard_ctx*)vctx;
-    const int R = srt_comm_size(ctx->comm);
-    for (int q = 0; q < R; q++) {
+    const dense_build* ctx = (const dense_build*)vctx;
+    for (int q = 0; q < ctx->R; q++) {
         int32_t qb, qe;
-        srt_shard_rows(ctx->ld, SRT_SHARD_ALIGN, R, q, &qb, &qe);
+        srt_shard_rows(ctx->ld, SRT_SHARD_ALIGN, ctx->R, q, &qb, &qe);
         if (k0 >= qb && k0 < qe) return q;
     }
     return 0;
 }
 
 static int shard_bcast(void* vctx, void* panel, size_t bytes, int owner, hipStream_t st) {
-    const shard_ctx* ctx = (const shard_ctx*)vctx;
-    return srt_coll_bcast(ctx->comm, panel, bytes, owner, st);
+    return srt_coll_bcast(((const dense_build*)vctx)->comm, panel, bytes, owner, st);
 }
 
 static int shard_gather(void* vctx, dense_ws* ws, int n, int phase, int32_t total, hipStream_t st) {
     (void)total;
-    shard_ctx* ctx = (shard_ctx*)vctx;
-    const int R = srt_comm_size(ctx->comm);
+    const dense_build* ctx = (const dense_build*)vctx;
+    const int R = ctx->R;
     if (phase == 0) /* counts are zero outside each rank's rows: a sum all-reduce assembles them */
         return srt_coll_allreduce_i32(ctx->comm, ws->cnt, (size_t)n, 0, st);
     /* every rank filled its own rows' contiguous arc segment: broadcast each segment */
@@ -2870,110 +2767,157 @@ static int shard_gather(void* vctx, dense_ws* ws, int n, int phase, int32_t tota
         e = min(e, n);
         const size_t o = (size_t)hptr[b], c = (size_t)(hptr[e] - hptr[b]);
         if (c == 0) continue;
-        rc = srt_coll_bcast(ctx->comm, ws->col + o, c * sizeof(int32_t), q, st);
-        if (!rc) rc = srt_coll_bcast(ctx->comm, ws->aw + o, c * sizeof(uint32_t), q, st);
-        if (!rc) rc = srt_coll_bcast(ctx->comm, ws->ar + o, c * sizeof(double), q, st);
+        rc = srt_coll_bcast(ctx->comm, ws->col.p + o, c * sizeof(int32_t), q, st);
+        if (!rc) rc = srt_coll_bcast(ctx->comm, ws->aw.p + o, c * sizeof(uint32_t), q, st);
+        if (!rc) rc = srt_coll_bcast(ctx->comm, ws->ar.p + o, c * sizeof(double), q, st);
     }
     const int rc2 = srt_coll_group_end(ctx->comm);
     free(hptr);
     return rc ? rc : rc2;
 }
 
-int srt_dense_build_sharded_ms(srt_comm* comm, int32_t n, int32_t ld, int32_t directed,
-                               const uint32_t* w_rows, const double* r_rows, uint32_t* lat_rows,
-                               double* rel_rows, double* lms_rows, uint64_t quantum_ns,
-                               hipStream_t st, int32_t fw_block, srt_build_stats* stats) {
-    if (!comm || n <= 0 || ld < n || ld % SRT_SHARD_ALIGN || !w_rows || !r_rows || !lat_rows || !rel_rows) {
-        srt_set_error("srt_dense_build_sharded: bad arguments");
-        return SRT_E_ARG;
+/* every timed tier starts the event pool over */
+static void evpool_restart(evpool_t* evp) {
+    if (!evp) return;
+    evp->used = 0;
+    evp->group = 2;
+}
+
+/* Dial levels (levels.hip) instead of the FW when the graph's distances are small enough for the
+ * level budget to beat the FW's predicted time (61 T relaxations/s, the measured update rate;
+ * symmetric rounds do half the relaxations, plus the rounds' chain). n >= 4,096: below that the
+ * FW's squaring or rounds
+ * cost less than the levels' launches. SRT_FORM levels=0 keeps the FW, =1 tries the levels at any
+ * size. *exact = 1 when the levels settled every pair (the u16 matrix and lat rows are final). */
+static int dense_try_levels(const dense_build& b, int* exact) {
+    *exact = 0;
+    const int mode = srt_form_int("levels", -1);
+    if (mode == 0 || (mode < 0 && b.n < 4096) || b.ld % 128) return SRT_OK;
+    /* relaxations at the update's rate + ~50 us of round chain per 128 pivots, for the largest
+     * shard (the same on every rank; srt_levels_build also agrees the budget by a min all-reduce) */
+    int max_rows = b.nrows;
+    for (int q = 0; q < b.R && b.R > 1; q++) {
+        int32_t qb = 0, qe = 0;
+        srt_shard_rows(b.ld, SRT_SHARD_ALIGN, b.R, q, &qb, &qe);
+        max_rows = max(max_rows, qe - qb);
     }
-    if (n > srt_dense_max_n()) { /* refused before any FW round runs */
-        srt_set_error("dense build supports n <= %d (n = %d); use the sparse SSSP", srt_dense_max_n(), n);
-        return SRT_E_RANGE;
-    }
-    if (fw_block != 0 && fw_block != B) {
-        srt_set_error("srt_dense_build_sharded: fw_block must be 0 or %d", B);
-        return SRT_E_ARG;
-    }
-    const int R = srt_comm_size(comm), me = srt_comm_rank(comm);
-    int32_t b, e;
-    srt_shard_rows(ld, SRT_SHARD_ALIGN, R, me, &b, &e);
-    const int nr = e - b;
-    dense_ws* ws;
-    int rc = ws_get(&ws, n);
+    const double fw_ms =
+        (double)max_rows * b.ld * b.ld / (b.directed ? 1.0 : 2.0) / 6.1e10 + b.ld / 128 * 0.05;
+    evpool_restart(b.evp);
+    int nlev = 0;
+    int64_t bytes = 0;
+    const int rc = srt_fw16_levels(b.comm, b.n, b.ld, b.row0, b.nrows, b.directed, b.w, b.r, b.lat,
+                                   b.st, b.evp, mode > 0 ? 1e30 : fw_ms, &nlev, &bytes);
     if (rc) return rc;
-    size_t pc = ws->panel_cap;
-    if ((rc = ws_grow((void**)&ws->panel, &pc, (size_t)B * ld, sizeof(uint32_t)))) return rc;
-    ws->panel_cap = pc;
+    if (b.stats) {
+        b.stats->levels = nlev;
+        b.stats->work_bytes = nlev ? bytes : 0;
+    }
+    *exact = nlev > 0;
+    return SRT_OK;
+}
+
+/* The distances into b.lat by the narrowest exact encoding: Dial levels (small distances) ->
+ * f16-compare u16 -> pk_min u16 -> u32. *enc: the SRT_DENC_* that served; *exact: a level build or
+ * a u16 tier did (srt_fw16_matrix() then holds the distances too). */
+static int dense_distances(const dense_build& b, int* enc, int* exact) {
+    const srt_comm* comm = b.comm;
+    const int n = b.n, ld = b.ld, R = b.R;
+    hipStream_t st = b.st;
+    void* ctx = const_cast<dense_build*>(&b);
+    int rc;
+    *enc = SRT_DENC_U32;
+    if ((rc = dense_try_levels(b, exact))) return rc;
+    if (*exact) *enc = SRT_DENC_LEVELS;
+    /* symmetric rounds up to 1,024 tile columns (fw16.hip SYM_TMAX, the panel-position table) */
+    const bool sym = !b.directed && R > 1 && ld <= 1024 * 128 && srt_form_int("sym", 1) != 0;
+    /* the u16 tiers need ld % 128 == 0 (every shard has it; one GPU may come with ld % 64) */
+    for (int fm = 1; fm >= 0 && !*exact && ld % 128 == 0; --fm) {
+        evpool_restart(b.evp);
+        /* what a tier of a sharded build is reported as; one GPU: srt_fw16_build says which of its
+         * forms ran (squaring, symmetric rounds of 64 / 128 / 256 pivots, every tile) */
+        int tier = fm ? (sym ? SRT_DENC_F16CMP_SYMSH128 : SRT_DENC_F16CMP) : SRT_DENC_U16;
+        if (fm && sym) /* undirected: each rank updates half of its row block (fw16.hip) */
+            rc = srt_fw16_build_sym_sharded(comm, n, ld, b.row0, b.nrows, b.w, b.lat, st, b.evp, exact);
+        else if (comm) /* a communicator of one rank included: the owner hook, no symmetric form */
+            rc = srt_fw16_build(n, ld, b.row0, b.nrows, b.w, b.lat, st, b.evp, shard_owner,
+                                R > 1 ? shard_bcast : NULL, ctx, b.me, fm, 0, NULL, exact);
+        else
+            rc = srt_fw16_build(n, ld, 0, ld, b.w, b.lat, st, b.evp, NULL, NULL, NULL, 0, fm,
+                                !b.directed, &tier, exact);
+        if (rc) return rc;
+        if (R > 1) { /* every rank must agree before falling back to a wider encoding */
+            int32_t* flag = b.ws->cnt;
+            SRT_HIPCHK(hipMemcpyAsync(flag, exact, sizeof(int32_t), hipMemcpyHostToDevice, st));
+            if ((rc = srt_coll_allreduce_i32(comm, flag, 1, 1, st))) return rc;
+            SRT_HIPCHK(hipMemcpyAsync(exact, flag, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            SRT_HIPCHK(hipStreamSynchronize(st));
+        }
+        if (*exact) *enc = tier;
+    }
+    if (*exact) return SRT_OK;
+    /* u32 rounds: ld not a multiple of 128, or a distance reached 0x7FFF quanta. The owner of the
+     * pivot rows closes them in place and (R > 1) broadcasts the panel. */
+    evpool_restart(b.evp);
+    if (b.nrows > 0) {
+        init_dist_kernel<<<dim3(srt_ceil_div(ld, 256), b.nrows), 256, 0, st>>>(n, ld, b.row0, b.w, b.lat);
+        SRT_HIPCHK(hipGetLastError());
+    }
+    for (int k0 = 0; k0 < ld; k0 += B) {
+        const int owner = comm ? shard_owner(ctx, k0) : b.me;
+        uint32_t* P = b.ws->panel.p;
+        if (owner == b.me) {
+            P = b.lat + (size_t)(k0 - b.row0) * ld;
+            if ((rc = fw_owner_part(b.lat, ld, b.row0, b.nrows, P, k0, st))) return rc;
+        }
+        if (R > 1 && (rc = srt_coll_bcast(comm, P, (size_t)B * ld * sizeof(uint32_t), owner, st)))
+            return rc;
+        if ((rc = fw_shard_part(b.lat, ld, b.row0, b.nrows, P, k0, st, b.evp))) return rc;
+    }
+    return SRT_OK;
+}
+
+/* The tables from the distances: the post pass for the form that built them, the diagonal rule
+ * and, when asked for, the f64 path-order ms rows. */
+static int dense_tables(const dense_build& b, int enc, int exact, double* lms, uint64_t quantum_ns) {
+    post_state ps;
+    int rc;
+    if (enc == SRT_DENC_LEVELS) /* predecessors from the level planes */
+        rc = dense_post_levels(b, &ps);
+    else /* R > 1: the essential arcs of every rank's rows, gathered */
+        rc = dense_post(b, exact ? srt_fw16_matrix() : NULL, b.R > 1 ? shard_gather : NULL,
+                        const_cast<dense_build*>(&b), &ps);
+    if (rc) return rc;
+    if ((rc = dense_finish_rows(b, ps))) return rc;
+    return lms ? dense_path_ms(b, ps, quantum_ns, lms) : SRT_OK;
+}
+
+/* The build behind both entry points (arguments checked): comm NULL for one GPU. */
+static int dense_build_run(const srt_comm* comm, int32_t n, int32_t ld, int32_t directed,
+                           const uint32_t* w, const double* r, uint32_t* lat, double* rel,
+                           double* lms, uint64_t quantum_ns, hipStream_t st,
+                           srt_build_stats* stats) {
+    const int R = comm ? srt_comm_size(comm) : 1, me = comm ? srt_comm_rank(comm) : 0;
+    int32_t row0 = 0, end = ld;
+    if (comm) srt_shard_rows(ld, SRT_SHARD_ALIGN, R, me, &row0, &end);
+    const int32_t nrows = end - row0, lrows = max(0, min(nrows, n - row0));
+    dense_build b = {comm, R, me, n, ld, row0, nrows, lrows, directed, w, r, lat, rel, st, stats,
+                     /* evp */ NULL, /* ws */ NULL};
+    int rc = ws_get(&b.ws, n);
+    if (rc) return rc;
+    /* the received pivot panel of the u32 rounds */
+    if (comm && (rc = b.ws->panel.need((size_t)B * ld))) return rc;
     build_events ev;
     if ((rc = ev.create())) return rc;
     hipEvent_t e0 = ev.e[0], e1 = ev.e[1], e2 = ev.e[2];
     SRT_HIPCHK(hipEventRecord(e0, st));
-    evpool_t* evp = NULL;
-    if (stats && stats->time_kernels && (rc = evpool_begin(&evp, ld / B))) return rc;
-    shard_ctx ctx = {comm, ld};
-    srt_comm_timing(comm, stats && stats->time_kernels);
+    const bool timed = stats && stats->time_kernels;
+    if (timed && (rc = evpool_begin(&b.evp, ld / B))) return rc;
+    if (comm) srt_comm_timing(comm, timed);
     int exact = 0, enc = SRT_DENC_U32;
-    /* symmetric rounds up to 1,024 tile columns (fw16.hip SYM_TMAX, the panel-position table) */
-    const bool sym = !directed && R > 1 && ld <= 1024 * 128 && srt_form_int("sym", 1) != 0;
-    if ((rc = dense_try_levels(comm, n, ld, b, nr, directed, w_rows, r_rows, lat_rows, st, evp, stats,
-                               &exact)))
-        return rc;
-    if (exact) enc = SRT_DENC_LEVELS;
-    for (int fm = 1; fm >= 0 && !exact; --fm) {
-        if (evp) {
-            evp->used = 0;
-            evp->group = 2;
-        }
-        if (fm && sym) /* undirected: each rank updates half of its row block (fw16.hip) */
-            rc = srt_fw16_build_sym_sharded(comm, n, ld, b, nr, w_rows, lat_rows, st, evp, &exact);
-        else
-            rc = srt_fw16_build(n, ld, b, nr, w_rows, lat_rows, st, evp, shard_owner,
-                                R > 1 ? shard_bcast : NULL, &ctx, me, fm, 0, NULL, &exact);
-        if (rc) return rc;
-        if (R > 1) { /* every rank must agree before falling back to a wider encoding */
-            int32_t* flag = ws->cnt;
-            SRT_HIPCHK(hipMemcpyAsync(flag, &exact, sizeof(int32_t), hipMemcpyHostToDevice, st));
-            if ((rc = srt_coll_allreduce_i32(comm, flag, 1, 1, st))) return rc;
-            SRT_HIPCHK(hipMemcpyAsync(&exact, flag, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            SRT_HIPCHK(hipStreamSynchronize(st));
-        }
-        if (exact)
-            enc = fm ? (sym ? SRT_DENC_F16CMP_SYMSH128 : SRT_DENC_F16CMP) : SRT_DENC_U16;
-    }
-    if (!exact) {
-        if (evp) {
-            evp->used = 0;
-            evp->group = 2;
-        }
-        if (nr > 0) {
-            dim3 g(srt_ceil_div(ld, 256), nr);
-            init_dist_kernel<<<g, 256, 0, st>>>(n, ld, b, w_rows, lat_rows);
-            SRT_HIPCHK(hipGetLastError());
-        }
-        for (int k0 = 0; k0 < ld; k0 += B) {
-            const int owner = shard_owner(&ctx, k0);
-            uint32_t* P;
-            if (owner == me) {
-                P = lat_rows + (size_t)(k0 - b) * ld;
-                if ((rc = fw_owner_part(lat_rows, ld, b, nr, P, k0, st))) return rc;
-            } else {
-                P = ws->panel;
-            }
-            if (R > 1 && (rc = srt_coll_bcast(comm, P, (size_t)B * ld * sizeof(uint32_t), owner, st)))
-                return rc;
-            if ((rc = fw_shard_part(lat_rows, ld, b, nr, P, k0, st, evp))) return rc;
-        }
-    }
+    if ((rc = dense_distances(b, &enc, &exact))) return rc;
     SRT_HIPCHK(hipEventRecord(e1, st));
-    rc = dense_post(n, ld, b, nr, directed, w_rows, r_rows, lat_rows,
-                    exact ? srt_fw16_matrix() : NULL, rel_rows, st, stats,
-                    R > 1 ? shard_gather : NULL, &ctx, enc == SRT_DENC_LEVELS);
-    if (rc) return rc;
-    if ((rc = dense_finish_rows(n, ld, b, nr, w_rows, r_rows, lat_rows, rel_rows, st, stats))) return rc;
-    if (lms_rows) {
-        if ((rc = dense_path_ms(n, ld, b, nr, lat_rows, quantum_ns, lms_rows, st))) return rc;
-    }
+    if ((rc = dense_tables(b, enc, exact, lms, quantum_ns))) return rc;
     SRT_HIPCHK(hipEventRecord(e2, st));
     if (stats) {
         SRT_HIPCHK(hipEventSynchronize(e2));
@@ -2986,11 +2930,58 @@ int srt_dense_build_sharded_ms(srt_comm* comm, int32_t n, int32_t ld, int32_t di
         stats->ms_fw = a;
         stats->ms_post = c;
         stats->ms_total = a + c;
-        if (evp && (rc = evpool_sum(evp, e2, stats))) return rc;
-        stats->ms_comm = srt_comm_timing_ms(comm);
+        if (b.evp && (rc = evpool_sum(b.evp, e2, stats))) return rc;
+        if (comm) stats->ms_comm = srt_comm_timing_ms(comm);
     }
-    srt_comm_timing(comm, 0);
+    if (comm) srt_comm_timing(comm, 0);
     return SRT_OK;
+}
+
+/* what both entry points refuse alike, after their own argument checks */
+static int dense_build_check(const char* who, int32_t n, int32_t fw_block) {
+    if (n > srt_dense_max_n()) { /* refused before any FW round runs */
+        srt_set_error("dense build supports n <= %d (n = %d); use the sparse SSSP", srt_dense_max_n(), n);
+        return SRT_E_RANGE;
+    }
+    if (fw_block != 0 && fw_block != B) {
+        srt_set_error("%s: fw_block must be 0 or %d", who, B);
+        return SRT_E_ARG;
+    }
+    return SRT_OK;
+}
+
+int srt_dense_build_device_ms(int32_t n, int32_t ld, int32_t directed, const uint32_t* w,
+                              const double* r, uint32_t* lat, double* rel, double* lat_ms,
+                              uint64_t quantum_ns, hipStream_t st, int32_t fw_block,
+                              srt_build_stats* stats) {
+    if (n <= 0 || ld < n || ld % B || !w || !r || !lat || !rel) {
+        srt_set_error("srt_dense_build_device: bad arguments (n=%d ld=%d)", n, ld);
+        return SRT_E_ARG;
+    }
+    const int rc = dense_build_check("srt_dense_build_device", n, fw_block);
+    if (rc) return rc;
+    return dense_build_run(NULL, n, ld, directed, w, r, lat, rel, lat_ms, quantum_ns, st, stats);
+}
+
+extern "C" int srt_dense_build_device(int32_t n, int32_t ld, int32_t directed, const uint32_t* w,
+                                      const double* r, uint32_t* lat, double* rel, void* stream,
+                                      int32_t fw_block, srt_build_stats* stats) {
+    return srt_dense_build_device_ms(n, ld, directed, w, r, lat, rel, NULL, 0, (hipStream_t)stream,
+                                     fw_block, stats);
+}
+
+int srt_dense_build_sharded_ms(srt_comm* comm, int32_t n, int32_t ld, int32_t directed,
+                               const uint32_t* w_rows, const double* r_rows, uint32_t* lat_rows,
+                               double* rel_rows, double* lms_rows, uint64_t quantum_ns,
+                               hipStream_t st, int32_t fw_block, srt_build_stats* stats) {
+    if (!comm || n <= 0 || ld < n || ld % SRT_SHARD_ALIGN || !w_rows || !r_rows || !lat_rows || !rel_rows) {
+        srt_set_error("srt_dense_build_sharded: bad arguments");
+        return SRT_E_ARG;
+    }
+    const int rc = dense_build_check("srt_dense_build_sharded", n, fw_block);
+    if (rc) return rc;
+    return dense_build_run(comm, n, ld, directed, w_rows, r_rows, lat_rows, rel_rows, lms_rows,
+                           quantum_ns, st, stats);
 }
 
 extern "C" int srt_dense_build_sharded(srt_comm* comm, int32_t n, int32_t ld, int32_t directed,

@@ -234,10 +234,6 @@ int srt_fw16_rows(int n, int ld, int nsub, const int32_t* dverts, const uint32_t
                   uint16_t* ds, uint32_t* lat_rows, hipStream_t st, int* exact, int* small,
                   int* passes);
 
-int srt_dense_post_device(int32_t n, int32_t ld, int32_t directed, const uint32_t* w,
-                          const double* r, uint32_t* d, const uint16_t* d16, double* rel,
-                          hipStream_t st, srt_build_stats* stats, int lvl);
-
 /* Largest dense n: the predecessor keys pack a 16-bit rank and the essential-arc offsets are
  * int32 (n^2 < 2^31), rounded down to the 128 tile. */
 #define SRT_DENSE_MAX_N 46336

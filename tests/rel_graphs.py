@@ -46,26 +46,26 @@ def ld_of(n):
 
 
 def tree_cap(n, packed=False):
-    """rel_tree_launch (dense.hip:1265-1286): the slots of rel_tree_kernel's size classes."""
+    """rel_tree_launch (dense.hip:1274-1295): the slots of rel_tree_kernel's size classes."""
     return 1024 if n <= 1024 else 4096 if n <= 4096 else 8192 if packed else 7168
 
 
 def deep_cap(n):
-    """rel_rows_launch (dense.hip:1860-1861): rel_deep_kernel's slots, 14 B each in 160 KB less
+    """rel_fw_rows (dense.hip:1874-1875): rel_deep_kernel's slots, 14 B each in 160 KB less
     1 KB of static LDS, the bitmap with its prefix and the 1,024 buckets."""
     fixed = 8 * (ld_of(n) >> 5) + 4 * 1024
     return min(n, (160 * 1024 - 1024 - fixed) // 14) & ~63
 
 
 def pk_cap(n, ntab):
-    """rel_pk_launch (dense.hip:1477-1478): rel_pk_kernel's slots, 12 B each in 80 KB less the
+    """rel_pk_launch (dense.hip:1486-1487): rel_pk_kernel's slots, 12 B each in 80 KB less the
     bitmap with its prefix and the reliability table."""
     fixed = 8 * (ld_of(n) >> 5) + 8 * ((ntab + 2) & ~1)
     return min(n, (80 * 1024 - fixed) // 12) & ~63
 
 
 def pk_width(n):
-    """rel_pk_launch (dense.hip:1481-1484): the 16-byte pieces per thread, K of rel_pk_kernel<K>."""
+    """rel_pk_launch (dense.hip:1490-1493): the 16-byte pieces per thread, K of rel_pk_kernel<K>."""
     k = (ld_of(n) + 2047) // 2048
     return next(x for x in (1, 2, 4, 8, 16) if k <= x)
 
@@ -79,18 +79,18 @@ def distinct_rel(g):
 def stage_of(path, n, mx, parents, ntab=0):
     """The kernel that finishes a row of range mx with `parents` parents."""
     if path == FW:
-        if mx <= 64 and parents <= tree_cap(n):           # rel_tree_kernel's bail, dense.hip:1187
+        if mx <= 64 and parents <= tree_cap(n):           # rel_tree_kernel's bail, dense.hip:1196
             return TREE
-        if mx < 1024 and parents <= deep_cap(n):          # rel_deep_kernel's, dense.hip:1712
+        if mx < 1024 and parents <= deep_cap(n):          # rel_deep_kernel's, dense.hip:1716
             return DEEP
-        return ORDER if mx < 1024 else SWEEPS             # rel_order_kernel's, dense.hip:1558
-    if path == FW_LEVELS:                                 # rel_levels_kernel's, dense.hip:1027
+        return ORDER if mx < 1024 else SWEEPS             # rel_order_kernel's, dense.hip:1562
+    if path == FW_LEVELS:                                 # rel_levels_kernel's, dense.hip:1036
         return LEVELS if mx <= 64 else SWEEPS
-    if path == ROWS:                                      # no deep or order stage, dense.hip:1859
+    if path == ROWS:                                      # no deep or order stage, dense.hip:2627
         return TREE if mx <= 64 and parents <= tree_cap(n) else SWEEPS
-    if path == LV_PK:                                     # rel_pk_kernel's bail, dense.hip:1397
+    if path == LV_PK:                                     # rel_pk_kernel's bail, dense.hip:1406
         return PK if parents <= pk_cap(n, ntab) else SWEEPS
-    if path in (LV_TREE_PK, LV_TREE_16):                  # dense.hip:1280, 1187
+    if path in (LV_TREE_PK, LV_TREE_16):                  # dense.hip:1289, 1196
         return TREE if mx <= 64 and parents <= tree_cap(n, path == LV_TREE_PK) else SWEEPS
     raise ValueError(path)
 
