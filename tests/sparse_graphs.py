@@ -36,7 +36,7 @@ _cache = {}
 
 def canon(g):
     """srt_canon_build of g on the CPU: quantum, largest weight, distance bound, arc count, row
-    pointers, arc weights and reliabilities (computed once per graph object)."""
+    pointers, arc heads (columns), weights and reliabilities (computed once per graph object)."""
     if getattr(g, "_canon", None) is None:
         L = _lib.lib()
         src = np.ascontiguousarray(g.src, np.int32)
@@ -54,7 +54,8 @@ def canon(g):
         g._canon = {"q": int(c.quantum_ns), "max_w_q": int(c.max_w_q),
                     "dist_bound": int(c.dist_bound), "wide": int(c.wide), "arcs": int(c.arcs),
                     "rp": rp, "deg": np.diff(rp),
-                    "w": np.ctypeslib.as_array(c.w, (max(m, 1),))[:m].copy(),
+                    "col": np.ctypeslib.as_array(c.col, (max(m, 1),))[:m].copy(),
+                    "w":np.ctypeslib.as_array(c.w, (max(m, 1),))[:m].copy(),
                     "r": np.ctypeslib.as_array(c.r, (max(m, 1),))[:m].copy()}
         L.srt_canon_free.argtypes = [ctypes.c_void_p]
         L.srt_canon_free(ctypes.byref(c))

@@ -14,15 +14,19 @@ depend on the row, and an arc is tight for s exactly when it is tight for some o
 direct arc (s, t) when t is a neighbour. The reliability must still be the path-order product from s
 (topology.c:1364-1365), so it is re-formed from these predecessors, not taken from k's row.
 
-This script checks both claims against the oracle's Dijkstra rows on a small BA graph, then prints
-the traffic model of the C5 split. usage: python tools/c5_derive_model.py [n]"""
+This script checks both claims against the oracle's Dijkstra rows on a small BA graph (the check
+itself is tests/derive_graphs.py model_check, which test_derive_graphs.py runs on constructed
+graphs of other degrees, depths and components), then prints the traffic model of the C5 split.
+usage: python tools/c5_derive_model.py [n]"""
 import os
 import sys
 
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
+sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "tests"))
 import oracle  # noqa: E402
+from derive_graphs import INF, model_check  # noqa: E402
 from shadow_amd import graphs  # noqa: E402
 
 
@@ -67,37 +71,11 @@ def main():
     inI = independent_low_degree(ptr, col, 4)
     el = oracle.EdgeList(g.n, g.directed, g.src, g.dst, g.lat_ns, g.loss)
     rows = oracle.sssp_rows(el, 0, n, nthreads=8, want_pred=True)
-    D = (rows["lat_int"] // np.uint64(q)).astype(np.int64)
-    P = rows["pred"]
+    unreached = rows["lat_int"] == np.uint64(0xFFFFFFFFFFFFFFFF)
+    D = np.where(unreached, np.uint64(INF), rows["lat_int"] // np.uint64(q)).astype(np.int64)
     I = np.nonzero(inI)[0]
-    wq = {}
-    for v in range(n):
-        for k in range(ptr[v], ptr[v + 1]):
-            wq[(v, int(col[k]))] = int(w[k])
-    bad_d = bad_p = 0
-    for s in I:
-        nb = col[ptr[s]:ptr[s + 1]]
-        ws = w[ptr[s]:ptr[s + 1]]
-        assert not inI[nb].any(), "not independent"
-        cand = ws[:, None] + D[nb]  # [deg, n]
-        dd = cand.min(axis=0)
-        dd[s] = 0
-        bad_d += int((dd != D[s]).sum())
-        for t in range(n):
-            if t == s:
-                continue
-            best = None
-            for i, k in enumerate(nb):
-                if cand[i, t] != dd[t]:
-                    continue
-                if t == k:
-                    key = (-int(ws[i]), int(s))  # the direct arc (s, k)
-                else:
-                    u = int(P[k, t])
-                    key = (-wq[(u, t)], u)
-                best = key if best is None or key < best else best
-            if best is None or best[1] != int(P[s, t]):
-                bad_p += 1
+    # both claims, as tests/derive_graphs.py checks them on its constructed graphs
+    bad_d, bad_p = model_check(ptr, col, w, inI, D, rows["pred"], I)
     print(f"BA n={n}: |I| = {len(I)} ({len(I) / n:.1%}), derived distances wrong: {bad_d}, "
           f"derived predecessors wrong: {bad_p}")
     # C5 traffic model (n = 100,000, m = 3): |I| and the mean degree in I from the real graph
