@@ -356,6 +356,57 @@ int srt_build_link_load(const srt_edges* g, const srt_build_opts* opts, int32_t 
                         const int32_t* dtgt, const uint64_t* dval, srt_link_load** out);
 void srt_link_load_free(srt_link_load* ll);
 
+/* ---- reliability envelope: the bounds over every shortest-path tie order (envelope.hip) -----
+ * The reference's Dijkstra takes as predecessor of t the first tight in-neighbour its heap pops:
+ * one of those with the smallest D[s][u], the heap order deciding among equals. With M(s, t) that
+ * set (the tight in-arcs u -> t of the canonical arcs with the smallest D[s][u], D[s][s] taken as
+ * 0) and r(u, t) the arc reliability of the table build:
+ *   hi(s, t) = max over u in M(s, t) of hi(s, u) * r(u, t)
+ *   lo(s, t) = min over u in M(s, t) of lo(s, u) * r(u, t),   hi(s, s) = lo(s, s) = 1.0
+ * one f64 multiply each: bit for bit the largest and smallest left-to-right product over every
+ * path a heap order can yield (f64 multiplication by r >= 0 is monotone). The tables' own
+ * reliability lies in [lo, hi]. Unreachable t: lo = hi = 0.0; t == s: lo = hi = 1.0 (the
+ * path-to-self rule is not exported). The containment statement holds on graphs of whole-ms
+ * edges, where the reference's ties are ties of equal integers too. */
+typedef struct srt_envelope_stats {
+    double ms_tables;        /* distance rows; srt_build_rel_envelope only */
+    double ms_envelope;      /* HIP events around the pass alone (dense: the essential-arc
+                              * compaction and the reliability gather included) */
+    int64_t tied_pairs;      /* |M| >= 2: srt_build_stats.tied_pairs over the same rows */
+    int64_t exposed_pairs;   /* tied, or some member of M exposed: the path depends on heap order */
+    int64_t sensitive_pairs; /* lo != hi bitwise: the value does */
+    int32_t max_sweeps;      /* the longest chain of the rows of the call, in arcs */
+    int32_t stage_forms;     /* bit f-1 set when some row took staging form f */
+} srt_envelope_stats;
+
+/* Largest n whose distance row is staged in LDS as u32 beside the pass's bitmaps (form 1); form 3
+ * reads the row from global memory, and its value is the largest n the pass takes at all. There
+ * is no form 2 (0). */
+int srt_envelope_stage_max_n(int form);
+/* Device entry points, with the conventions of the route entries: every pointer is a device
+ * pointer, either output may be NULL, outputs have row stride ldo (>= n; columns >= n are never
+ * written), the calls return after their work on the stream has finished.
+ * Rows of a sparse graph: row i (of lat_rows, stride ldl, and of the outputs) belongs to srcs[i],
+ * or src_begin + i when srcs is NULL. SRT_E_RANGE for a graph whose distances need u64 rows. */
+int srt_envelope_rows_device(const srt_sparse_graph* g, int32_t nsrc, const int32_t* srcs,
+                             int32_t src_begin, const uint32_t* lat_rows, size_t ldl,
+                             double* rel_lo, double* rel_hi, size_t ldo, void* stream,
+                             srt_envelope_stats* stats);
+/* Rows [row0, row0 + nrows) of a dense device graph (w, r) and its finished lat table (all
+ * ld x ld, as for srt_dense_build_device): output row i belongs to source row0 + i. */
+int srt_envelope_dense_device(int32_t n, int32_t ld, int32_t directed, const uint32_t* w,
+                              const double* r, const uint32_t* lat, int32_t row0, int32_t nrows,
+                              double* rel_lo, double* rel_hi, size_t ldo, void* stream,
+                              srt_envelope_stats* stats);
+/* The envelope of nsrc sources (srcs strictly increasing; NULL with nsrc = n: every vertex)
+ * towards every vertex: host outputs nsrc x n, either of them NULL. One GPU; the same choice of
+ * algorithm, chunks, front ends and refusals as srt_build_routes (a graph whose distances need u64
+ * rows: SRT_E_RANGE). use_shortest_path = 0: lo = hi = r(s, t) for t != s (SRT_E_INVALID unless the
+ * graph is complete, as the table build). */
+int srt_build_rel_envelope(const srt_edges* g, const srt_build_opts* opts, int32_t nsrc,
+                           const int32_t* srcs, double* rel_lo, double* rel_hi,
+                           srt_envelope_stats* stats);
+
 /* ---- multi-GPU (one process per GPU; RCCL over xGMI) ----------------------------------- */
 typedef struct srt_comm srt_comm;
 /* 128-byte RCCL unique id, created on rank 0 and shared by the caller (e.g. torch.distributed). */

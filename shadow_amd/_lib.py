@@ -89,6 +89,18 @@ class RouteStats(ctypes.Structure):
     ]
 
 
+class EnvelopeStats(ctypes.Structure):
+    _fields_ = [
+        ("ms_tables", ctypes.c_double),
+        ("ms_envelope", ctypes.c_double),
+        ("tied_pairs", ctypes.c_int64),
+        ("exposed_pairs", ctypes.c_int64),
+        ("sensitive_pairs", ctypes.c_int64),
+        ("max_sweeps", ctypes.c_int32),
+        ("stage_forms", ctypes.c_int32),
+    ]
+
+
 class LinkLoad(ctypes.Structure):
     _fields_ = [
         ("narcs", ctypes.c_int64),
@@ -159,6 +171,12 @@ SIGNATURES = {
                                                    _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "srt_build_link_load": (ctypes.c_int, [_VP, _VP, _I32, _VP, _I64, _VP, _VP, _VP, _VP]),
     "srt_link_load_free": (None, [_VP]),
+    "srt_envelope_stage_max_n": (ctypes.c_int, [ctypes.c_int]),
+    "srt_envelope_rows_device": (ctypes.c_int, [_VP, _I32, _VP, _I32, _VP, ctypes.c_size_t, _VP, _VP,
+                                                 ctypes.c_size_t, _VP, _VP]),
+    "srt_envelope_dense_device": (ctypes.c_int, [_I32, _I32, _I32, _VP, _VP, _VP, _I32, _I32, _VP,
+                                                  _VP, ctypes.c_size_t, _VP, _VP]),
+    "srt_build_rel_envelope": (ctypes.c_int, [_VP, _VP, _I32, _VP, _VP, _VP, _VP]),
     "srt_comm_unique_id": (ctypes.c_int, [_VP]),
     "srt_comm_init": (ctypes.c_int, [_VP, _I32, _I32, _I32, _VP]),
     "srt_comm_init_all": (ctypes.c_int, [_I32, _VP, _VP]),

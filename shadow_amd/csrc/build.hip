@@ -2199,7 +2199,8 @@ extern "C" int srt_routes_rows_device(const srt_sparse_graph* g, int32_t nsrc, c
 }
 
 /* The route rows of the sources verts (NULL: every vertex) on one GPU, a chunk at a time, for the
- * route export and the link load. route_source_open puts the distances' origin on the device (the
+ * route export, the link load and the reliability envelope (which takes the distance rows and
+ * the in-arc CSR alone: see `envelope`). route_source_open puts the distances' origin on the device (the
  * dense tables and their essential in-lists, or the sparse graph); route_source_chunks sizes the
  * chunk from the memory free at that point and allocates its rows; route_source_step computes the
  * rows of one chunk; route_source_close releases everything (after a failed open too). Start from
@@ -2212,13 +2213,19 @@ struct route_source {
     srt_sparse_graph* sg; /* sparse */
     uint32_t* dlat;       /* dense: the ld x ld table; sparse: the chunk's distance rows */
     double* drel;
+    double* dr;           /* dense: the ld x ld arc reliabilities */
     int32_t *ess_rp, *ess_col; /* dense: the essential in-lists (srt_routes_ess_build) */
     uint32_t* ess_w;
+    double* ess_r; /* ... and, for the envelope, their reliabilities (srt_envelope_ess_rel) */
     /* the in-arc CSR the route pass reads and the load is indexed by; sorted: its lists ascend */
     const int32_t *irp, *icol;
     const uint32_t* iw;
+    const double* ir; /* the arcs' reliabilities (dense: with `envelope` only) */
     int64_t narcs;
     int sorted;
+    int envelope;     /* set before the open: the envelope pass reads this source (ir, ms_ess_rel);
+                       * a step then runs the route pass only where a route output is wanted */
+    double ms_ess_rel;
     int chunk;        /* rows a step */
     int32_t* dout[3]; /* pred, first, hops of the last step's rows (stride n; NULL: not asked) */
     int cnt;          /* ... how many, and their sources (NULL: the vertices from the step's r0) */
@@ -2246,14 +2253,13 @@ static int route_source_open(route_source* s, const srt_canon* c, const srt_buil
     if (s->dense) {
         const size_t ll = (size_t)s->ld * s->ld;
         uint32_t* dw;
-        double* dr;
         TRY(check_dense_n(n));
         TRY(dalloc(&s->B, (void**)&dw, ll * sizeof(uint32_t)));
-        TRY(dalloc(&s->B, (void**)&dr, ll * sizeof(double)));
+        TRY(dalloc(&s->B, (void**)&s->dr, ll * sizeof(double)));
         TRY(dalloc(&s->B, (void**)&s->dlat, ll * sizeof(uint32_t)));
         TRY(dalloc(&s->B, (void**)&s->drel, ll * sizeof(double)));
-        TRY(dense_upload(c, s->ld, 0, s->ld, dw, dr, s->st, 1));
-        TRY(srt_dense_build_device_ms(n, s->ld, c->directed, dw, dr, s->dlat, s->drel, NULL,
+        TRY(dense_upload(c, s->ld, 0, s->ld, dw, s->dr, s->st, 1));
+        TRY(srt_dense_build_device_ms(n, s->ld, c->directed, dw, s->dr, s->dlat, s->drel, NULL,
                                       c->quantum_ns, s->st, opts ? opts->fw_block : 0, &bs));
         s->stats.ms_tables = bs.ms_total;
         TRY(srt_routes_ess_build(n, s->ld, c->directed, dw, s->dlat, s->st, &s->ess_rp, &s->ess_col,
@@ -2262,6 +2268,11 @@ static int route_source_open(route_source* s, const srt_canon* c, const srt_buil
         s->icol = s->ess_col;
         s->iw = s->ess_w;
         s->narcs = s->stats.ess_arcs;
+        if (s->envelope) {
+            TRY(srt_envelope_ess_rel(n, s->ld, s->narcs, s->ess_rp, s->ess_col, s->dr, s->st,
+                                     &s->ess_r, &s->ms_ess_rel));
+            s->ir = s->ess_r;
+        }
         /* an undirected graph's essential lists are compacted in column order, a directed one's
          * through per-head cursors in no order */
         s->sorted = c->directed ? 0 : 1;
@@ -2270,6 +2281,7 @@ static int route_source_open(route_source* s, const srt_canon* c, const srt_buil
         s->irp = s->sg->irp;
         s->icol = s->sg->icol;
         s->iw = s->sg->iw;
+        s->ir = s->sg->ir;
         s->narcs = s->sg->arcs;
         s->sorted = 1;
     }
@@ -2309,9 +2321,10 @@ static int route_source_step(route_source* s, int r0) {
         TRY(sparse_chunk(s->sg, s->dverts, r0, s->cnt, s->dlat, s->drel, NULL, s->st, &bs));
         s->stats.ms_tables += bs.ms_total;
     }
-    TRY(srt_routes_rows_timed(n, s->cnt, s->srcs, r0, s->dense, s->dlat,
-                              (size_t)(s->dense ? s->ld : n), s->irp, s->icol, s->iw, s->dout[0],
-                              s->dout[1], s->dout[2], (size_t)n, s->st, &s->stats));
+    if (!s->envelope || s->dout[0] || s->dout[1] || s->dout[2])
+        TRY(srt_routes_rows_timed(n, s->cnt, s->srcs, r0, s->dense, s->dlat,
+                                  (size_t)(s->dense ? s->ld : n), s->irp, s->icol, s->iw, s->dout[0],
+                                  s->dout[1], s->dout[2], (size_t)n, s->st, &s->stats));
 out:
     return rc;
 }
@@ -2319,6 +2332,7 @@ out:
 static void route_source_close(route_source* s) {
     if (s->st) {
         srt_routes_ess_free(s->ess_rp, s->ess_col, s->ess_w, s->st);
+        if (s->ess_r) (void)hipFreeAsync(s->ess_r, s->st);
         (void)hipStreamSynchronize(s->st);
         (void)hipStreamDestroy(s->st);
     }
@@ -2419,6 +2433,133 @@ extern "C" int srt_build_routes(const srt_edges* g, const srt_build_opts* opts, 
             return (int)SRT_E_RANGE;
         }
         return routes_one(c, opts, algo, nsrc, srcs, hout, stats);
+    });
+}
+
+/* ------------------------------------------------------------------------------------------ */
+/* Reliability envelope (envelope.hip): the distance rows of the route source, then the bounds  */
+/* over every tie order; no route output is wanted, so its steps skip the route pass.           */
+/* ------------------------------------------------------------------------------------------ */
+extern "C" int srt_envelope_rows_device(const srt_sparse_graph* g, int32_t nsrc, const int32_t* srcs,
+                                        int32_t src_begin, const uint32_t* lat_rows, size_t ldl,
+                                        double* rel_lo, double* rel_hi, size_t ldo, void* stream,
+                                        srt_envelope_stats* stats) {
+    if (!g || nsrc < 1 || !lat_rows || ldl < (size_t)g->n ||
+        (!srcs && (src_begin < 0 || (int64_t)src_begin + nsrc > g->n))) {
+        srt_set_error("srt_envelope_rows_device: bad arguments");
+        return SRT_E_ARG;
+    }
+    if (g->wide) {
+        srt_set_error("srt_envelope_rows_device: shortest-path latencies may pass the u32 range; the "
+                      "envelope pass reads u32 rows only");
+        return SRT_E_RANGE;
+    }
+    srt_envelope_stats local;
+    memset(&local, 0, sizeof(local));
+    const int rc = srt_envelope_rows(g->n, nsrc, srcs, src_begin, 0, lat_rows, ldl, g->irp, g->icol,
+                                     g->iw, g->ir, rel_lo, rel_hi, ldo, (hipStream_t)stream, &local);
+    if (!rc && stats) *stats = local;
+    return rc;
+}
+
+/* one GPU: the envelope of the route source's rows into the host outputs */
+static int envelope_one(const srt_canon* c, const srt_build_opts* opts, int algo, int nsub,
+                        const int32_t* verts, double* hlo, double* hhi, srt_envelope_stats* stats) {
+    const size_t n = (size_t)c->n, w8 = n * sizeof(double);
+    const bool none[3] = {false, false, false};
+    route_source src = {};
+    srt_envelope_stats es;
+    double *dlo = NULL, *dhi = NULL;
+    int rc = SRT_OK;
+    memset(&es, 0, sizeof(es));
+    src.envelope = 1;
+    TRY(route_source_open(&src, c, opts, algo, nsub, verts));
+    TRY(route_source_chunks(&src, 0, 2 * w8, none)); /* 16 B per pair: lo and hi */
+    TRY(dalloc(&src.B, (void**)&dlo, (size_t)src.chunk * w8));
+    TRY(dalloc(&src.B, (void**)&dhi, (size_t)src.chunk * w8));
+    for (int r0 = 0; r0 < nsub; r0 += src.chunk) {
+        TRY(route_source_step(&src, r0));
+        TRY(srt_envelope_rows(c->n, src.cnt, src.srcs, r0, src.dense, src.dlat,
+                              src.dense ? (size_t)src.ld : n, src.irp, src.icol, src.iw, src.ir, dlo,
+                              dhi, n, src.st, &es));
+        if (hlo) TRY(table_download(hlo + (size_t)r0 * n, w8, dlo, w8, w8, src.cnt, src.st, 1));
+        if (hhi) TRY(table_download(hhi + (size_t)r0 * n, w8, dhi, w8, w8, src.cnt, src.st, 1));
+    }
+    es.ms_tables = src.stats.ms_tables;
+    /* dense: the essential-arc compaction and the reliability gather count as the pass */
+    es.ms_envelope += src.stats.ms_routes + src.ms_ess_rel;
+    if (stats) *stats = es;
+out:
+    route_source_close(&src);
+    return rc;
+}
+
+/* direct mode: every pair is its own canonical arc (the smallest latency among parallel edges,
+ * then the lowest edge index, as graph.c) */
+static int envelope_direct(const srt_edges* g, int32_t nsrc, const int32_t* srcs, double* hlo,
+                           double* hhi) {
+    const size_t n = (size_t)g->n;
+    std::vector<int32_t> row_of(n, -1);
+    for (int32_t i = 0; i < nsrc; i++) row_of[(size_t)(srcs ? srcs[i] : i)] = i;
+    std::vector<int64_t> best;
+    std::vector<double> rel;
+    try {
+        best.assign((size_t)nsrc * n, INT64_MAX);
+        rel.assign((size_t)nsrc * n, 0.0);
+    } catch (const std::bad_alloc&) {
+        srt_set_error("srt_build_rel_envelope: out of memory for %d rows", nsrc);
+        return SRT_E_NOMEM;
+    }
+    auto offer = [&](int32_t u, int32_t v, int64_t e) {
+        if (u == v || row_of[(size_t)u] < 0) return;
+        const size_t o = (size_t)row_of[(size_t)u] * n + (size_t)v;
+        if (g->lat_ns[e] < best[o]) { /* strict: the lowest edge index keeps equal latencies */
+            best[o] = g->lat_ns[e];
+            rel[o] = 1.0f - g->loss[e];
+        }
+    };
+    for (int64_t e = 0; e < g->m; e++) {
+        offer(g->src[e], g->dst[e], e);
+        if (!g->directed) offer(g->dst[e], g->src[e], e);
+    }
+    for (int32_t i = 0; i < nsrc; i++) rel[(size_t)i * n + (size_t)(srcs ? srcs[i] : i)] = 1.0;
+    if (hlo) memcpy(hlo, rel.data(), rel.size() * sizeof(double));
+    if (hhi) memcpy(hhi, rel.data(), rel.size() * sizeof(double));
+    return SRT_OK;
+}
+
+extern "C" int srt_build_rel_envelope(const srt_edges* g, const srt_build_opts* opts, int32_t nsrc,
+                                      const int32_t* srcs, double* rel_lo, double* rel_hi,
+                                      srt_envelope_stats* stats) {
+    if (!g || g->n <= 0) {
+        srt_set_error("srt_build_rel_envelope: null argument");
+        return SRT_E_ARG;
+    }
+    if (check_verts(g->n, nsrc, srcs)) {
+        srt_set_error("srt_build_rel_envelope: the sources must be 1..n strictly increasing vertex "
+                      "indices (or NULL with nsrc = n)");
+        return SRT_E_ARG;
+    }
+    last_row_chunks.store(0, std::memory_order_relaxed);
+    const int use_sp = opts ? opts->use_shortest_path : 1;
+    if (!use_sp) {
+        int32_t* const none[3] = {NULL, NULL, NULL};
+        if (stats) memset(stats, 0, sizeof(*stats));
+        const int rc = routes_direct(g, 0, NULL, none); /* the completeness check and its error */
+        return rc ? rc : envelope_direct(g, nsrc, srcs, rel_lo, rel_hi);
+    }
+    if (srt_device_count() < 1) {
+        srt_set_error("srt_build_rel_envelope: no HIP device");
+        return SRT_E_DEVICE;
+    }
+    return with_canon(g, opts, 1, [&](const srt_canon* c, int algo, double) {
+        if (c->wide) {
+            srt_set_error("srt_build_rel_envelope: shortest-path latencies may pass the u32 range "
+                          "(bound %llu quanta of %llu ns); the envelope pass reads u32 rows only",
+                          (unsigned long long)c->dist_bound, (unsigned long long)c->quantum_ns);
+            return (int)SRT_E_RANGE;
+        }
+        return envelope_one(c, opts, algo, nsrc, srcs, rel_lo, rel_hi, stats);
     });
 }
 

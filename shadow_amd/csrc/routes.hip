@@ -279,14 +279,6 @@ __global__ __launch_bounds__(RT_THREADS) void routes_kernel(
     if (tid == 0 && form_mask) atomicOr(forms, form_mask);
 }
 
-static int rt_cus(void) {
-    int cus = 256, dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-        cus = prop.multiProcessorCount;
-    return cus;
-}
-
 #define RT_TRY(x)                                                                              \
     do {                                                                                       \
         hipError_t e_ = (x);                                                                   \
@@ -318,7 +310,7 @@ int srt_routes_rows(int n, int nrows, const int32_t* srcs, int src_begin, int by
     /* per-block scratch: the predecessor row where that output is NULL, the jump words of forms 2
      * and 3; the grid shrinks where it would pass RT_SCRATCH_BYTES */
     const size_t per_block = (size_t)n * ((pred ? 0 : sizeof(int32_t)) + (nform == 1 ? 0 : 8));
-    const int cus = rt_cus();
+    const int cus = srt_cu_count();
     int grid = lds > 76 * 1024 ? cus : 2 * cus; /* workgroups the LDS lets a CU hold */
     if (per_block && (size_t)grid * per_block > RT_SCRATCH_BYTES)
         grid = (int)(RT_SCRATCH_BYTES / per_block) > 0 ? (int)(RT_SCRATCH_BYTES / per_block) : 1;
@@ -454,29 +446,6 @@ __global__ __launch_bounds__(1024) void rt_scan_kernel(int n, const int32_t* __r
     if (tid == 1023) rp[n] = part[1023];
 }
 
-/* a HIP-event pair around a span of the stream */
-struct rt_span {
-    hipEvent_t e[2] = {nullptr, nullptr};
-    ~rt_span() {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-    int begin(hipStream_t st) {
-        SRT_HIPCHK(hipEventCreate(&e[0]));
-        SRT_HIPCHK(hipEventCreate(&e[1]));
-        SRT_HIPCHK(hipEventRecord(e[0], st));
-        return SRT_OK;
-    }
-    int end(hipStream_t st, double* ms) {
-        float a = 0;
-        SRT_HIPCHK(hipEventRecord(e[1], st));
-        SRT_HIPCHK(hipEventSynchronize(e[1]));
-        SRT_HIPCHK(hipEventElapsedTime(&a, e[0], e[1]));
-        *ms += a;
-        return SRT_OK;
-    }
-};
-
 /* irp (n + 1), icol, iw of the essential in-arcs on the device; *arcs = their number, *ms += the
  * HIP-event time of the compaction. The arrays come from the scratch pool: srt_routes_ess_free
  * returns them (stream-ordered). */
@@ -488,7 +457,7 @@ int srt_routes_ess_build(int n, int ld, int directed, const uint32_t* w, const u
     *iw = NULL;
     int32_t* cnt = NULL;
     int32_t total = 0;
-    rt_span span;
+    srt_event_span span;
     int rc = span.begin(st);
     if (rc) return rc;
     const int grid = srt_ceil_div(n, 4) < 4096 ? srt_ceil_div(n, 4) : 4096;
@@ -532,7 +501,7 @@ int srt_routes_rows_timed(int n, int nrows, const int32_t* srcs, int src_begin, 
                           const uint32_t* D, size_t ldd, const int32_t* irp, const int32_t* icol,
                           const uint32_t* iw, int32_t* pred, int32_t* first, int32_t* hops,
                           size_t ldo, hipStream_t st, srt_route_stats* stats) {
-    rt_span span;
+    srt_event_span span;
     int rc = span.begin(st);
     if (rc) return rc;
     int32_t mh = 0, forms = 0;

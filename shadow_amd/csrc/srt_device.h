@@ -26,6 +26,38 @@ static __device__ __forceinline__ void srt_max_once(int32_t* p, int v) {
         }                                                                                  \
     } while (0)
 
+/* a HIP-event pair around a span of a stream (the route and envelope passes' own times) */
+struct srt_event_span {
+    hipEvent_t e[2] = {nullptr, nullptr};
+    ~srt_event_span() {
+        for (hipEvent_t x : e)
+            if (x) (void)hipEventDestroy(x);
+    }
+    int begin(hipStream_t st) {
+        SRT_HIPCHK(hipEventCreate(&e[0]));
+        SRT_HIPCHK(hipEventCreate(&e[1]));
+        SRT_HIPCHK(hipEventRecord(e[0], st));
+        return SRT_OK;
+    }
+    int end(hipStream_t st, double* ms) {
+        float a = 0;
+        SRT_HIPCHK(hipEventRecord(e[1], st));
+        SRT_HIPCHK(hipEventSynchronize(e[1]));
+        SRT_HIPCHK(hipEventElapsedTime(&a, e[0], e[1]));
+        *ms += a;
+        return SRT_OK;
+    }
+};
+
+/* the CUs of the current device (256 when it cannot be asked): the persistent grids' unit */
+static inline int srt_cu_count(void) {
+    int cus = 256, dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
+        cus = prop.multiProcessorCount;
+    return cus;
+}
+
 /* Per-thread slot of the static per-device state (workspaces, event pools, FW buffers and
  * streams): the current device (0..63), or 64 + r for virtual rank r when several ranks share
  * one device inside one process (srt_build_tables_multi with SRT_VIRTUAL_RANKS, comm.hip). */
@@ -311,6 +343,18 @@ int srt_link_load_rows(int n, int nrows, const int32_t* srcs, int src_begin, con
  * of row r added into zeroed rows (tgt, val: device arrays those offsets index) */
 int srt_link_load_demand_rows(int n, int nrows, const int64_t* rowptr, const int32_t* tgt,
                               const uint64_t* val, uint64_t* dem, size_t ldd, hipStream_t st);
+/* envelope.hip: the reliability bounds lo / hi (either NULL) of nrows distance rows over an in-arc
+ * CSR with the arcs' reliabilities ir; rows, sources and strides as srt_routes_rows. Adds the
+ * HIP-event time, the counts, the sweeps and the staging forms to *stats; returns after the
+ * stream */
+int srt_envelope_rows(int n, int nrows, const int32_t* srcs, int src_begin, int by_src,
+                      const uint32_t* D, size_t ldd, const int32_t* irp, const int32_t* icol,
+                      const uint32_t* iw, const double* ir, double* lo, double* hi, size_t ldo,
+                      hipStream_t st, srt_envelope_stats* stats);
+/* r[u][t] of the essential in-arcs of srt_routes_ess_build, from the scratch pool (hipFreeAsync
+ * returns it); *ms += the gather's HIP-event time */
+int srt_envelope_ess_rel(int n, int ld, int64_t arcs, const int32_t* irp, const int32_t* icol,
+                         const double* r, hipStream_t st, double** ir, double* ms);
 /* collectives: all-gather of equal byte blocks, rank q's block at buf + q * bytes */
 int srt_coll_allgather(const srt_comm* c, void* buf, size_t bytes, hipStream_t st);
 

@@ -23,7 +23,8 @@ import struct
 import numpy as np
 
 from . import _lib
-from ._lib import BuildOpts, BuildStats, Edges, LinkLoad, LinkLoadStats, RouteStats, check, lib
+from ._lib import (BuildOpts, BuildStats, Edges, EnvelopeStats, LinkLoad, LinkLoadStats, RouteStats,
+                   check, lib)
 
 
 def ip_to_net(ip) -> int:
@@ -392,6 +393,31 @@ def build_routes(n, directed, src, dst, lat_ns, loss, sources=None, use_shortest
     return pred, first, hops, st
 
 
+def build_rel_envelope(n, directed, src, dst, lat_ns, loss, sources=None, use_shortest_path=True,
+                       device=0, algo=_lib.ALGO_AUTO):
+    """srt_build_rel_envelope on host arrays -> (lo, hi f64 [k, n], stats): the smallest and the
+    largest reliability of every pair over every order in which the reference's Dijkstra may break
+    its shortest-path ties, for the sources `sources` (strictly increasing; None = every vertex);
+    stats (EnvelopeStats) counts the tied, exposed and sensitive pairs."""
+    src = np.ascontiguousarray(src, np.int32)
+    dst = np.ascontiguousarray(dst, np.int32)
+    lat_ns = np.ascontiguousarray(lat_ns, np.int64)
+    loss = np.ascontiguousarray(loss, np.float64)
+    e = Edges(n, int(bool(directed)), len(src), src.ctypes.data, dst.ctypes.data,
+              lat_ns.ctypes.data, loss.ctypes.data)
+    o = BuildOpts(device, algo, int(bool(use_shortest_path)), 0)
+    ss = None if sources is None else np.ascontiguousarray(sources, np.int32)
+    k = n if ss is None else len(ss)
+    lo = np.empty((k, n), np.float64)
+    hi = np.empty((k, n), np.float64)
+    st = EnvelopeStats()
+    check(lib().srt_build_rel_envelope(ctypes.byref(e), ctypes.byref(o), k,
+                                       None if ss is None else ss.ctypes.data, lo.ctypes.data,
+                                       hi.ctypes.data, ctypes.byref(st)),
+          "srt_build_rel_envelope")
+    return lo, hi, st
+
+
 class LinkLoadInfo:
     """The scalar fields of srt_link_load."""
 
@@ -519,6 +545,20 @@ class SparseGraph:
                                            self.n if ldo is None else int(ldo),
                                            ctypes.c_void_p(stream), st),
               "srt_routes_rows_device")
+
+    def envelope_rows(self, lat_ptr, nsrc, lo_ptr=None, hi_ptr=None, srcs_ptr=None, src_begin=0,
+                      ldl=None, ldo=None, stream=None, stats=None):
+        """srt_envelope_rows_device over device pointers: row i of lat (stride ldl, default n) and of
+        the f64 outputs (stride ldo, default n; either may be None) belongs to srcs[i], or
+        src_begin + i without a source list."""
+        st = ctypes.byref(stats) if stats is not None else None
+        check(lib().srt_envelope_rows_device(self._h, int(nsrc), ctypes.c_void_p(srcs_ptr),
+                                             int(src_begin), ctypes.c_void_p(lat_ptr),
+                                             self.n if ldl is None else int(ldl),
+                                             ctypes.c_void_p(lo_ptr), ctypes.c_void_p(hi_ptr),
+                                             self.n if ldo is None else int(ldo),
+                                             ctypes.c_void_p(stream), st),
+              "srt_envelope_rows_device")
 
     def in_arcs(self):
         """Device pointers (rowptr, tails) of the in-arc CSR that link_load_rows' load indexes."""
