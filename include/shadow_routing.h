@@ -407,6 +407,75 @@ int srt_build_rel_envelope(const srt_edges* g, const srt_build_opts* opts, int32
                            const int32_t* srcs, double* rel_lo, double* rel_hi,
                            srt_envelope_stats* stats);
 
+/* ---- split load: the link load with every shortest-path tie split evenly (splitload.hip) -----
+ * The link load above charges a pair's demand to its canonical route, one arbitrary choice among
+ * the paths the reference's Dijkstra can return. Here each target's predecessor is drawn uniformly
+ * from M(s, t), the set of the envelope above, and the outputs are the expected traffic. For a
+ * source s with the demand row c(s, .), every reachable t != s has
+ *   inflow_s(t) = the sum of share_s(v) over the v with t in M(s, v)
+ *   f_s(t)      = (double)c(s, t) + inflow_s(t)
+ *   share_s(t)  = f_s(t) / (double)|M(s, t)|                       one f64 division
+ * and the source adds share_s(t) to load(u -> t) for every u in M(s, t) and inflow_s(t) to
+ * through(t) (a share that reaches s adds to no through word). Where no pair is tied this is the
+ * link load exactly. load and through are f64, summed with atomic adds across the sources, so two
+ * runs may differ in the last bits unless every partial sum is exact; an arc in no M, or whose
+ * targets carry no flow, gets no add: the arcs reported (load > 0) are an exact set. The totals
+ * are u64 and exact, as the link load's; a total demand of 2^53 or more is refused (SRT_E_RANGE),
+ * so every demand converts to f64 exactly. */
+typedef struct srt_split_load {
+    int64_t narcs;
+    int32_t *tail, *head;
+    double* load;    /* arcs with load > 0, by (tail, head) */
+    double* through; /* n */
+    uint64_t routed, unrouted, self_demand;
+    double ms_tables, ms_split; /* ms_split: HIP events around the pass alone */
+    int64_t tied_pairs; /* |M| >= 2 over every row of the call, with demand or without: the
+                         * envelope's tied_pairs over the same rows */
+    int32_t forms;      /* bit f-1 set when some row took staging form f */
+} srt_split_load;
+/* the pass of a device entry point */
+typedef struct srt_split_load_stats {
+    double ms_split;
+    int64_t tied_pairs;
+    int32_t max_sweeps; /* the longest chain of members of the rows that carried routed demand */
+    int32_t forms;
+} srt_split_load_stats;
+
+/* Largest n whose distance row, children counters and f64 inflow words live in LDS (form 1), or
+ * the row alone, the counters and inflow words in device memory (form 2); form 3 reads the row
+ * from device memory too, and its value is the largest n the pass takes at all. */
+int srt_split_load_stage_max_n(int form);
+/* Device entry point: every pointer is a device pointer. Row i of lat_rows (u32 quanta, stride
+ * ldl: the rows srt_sparse_graph_rows made) and of the u64 demand rows dem (stride ldd) belongs to
+ * srcs[i], or src_begin + i when srcs is NULL. The pass ADDS into load (one f64 word per in-arc of
+ * the graph, in the order of srt_sparse_graph_in_arcs), through (n f64 words) and totals (routed,
+ * unrouted, self; u64): the caller zeroes them before the first call and keeps the total demand
+ * below 2^53. SRT_E_RANGE for a graph whose distances need u64 rows. Returns after the stream. */
+int srt_split_load_rows_device(const srt_sparse_graph* g, int32_t nsrc, const int32_t* srcs,
+                               int32_t src_begin, const uint32_t* lat_rows, size_t ldl,
+                               const uint64_t* dem, size_t ldd, double* load, double* through,
+                               uint64_t* totals, void* stream, srt_split_load_stats* stats);
+/* Rows [row0, row0 + nrows) of a dense device graph and its finished lat table (as for
+ * srt_routes_dense_device; row i of dem belongs to source row0 + i): load is indexed by the
+ * essential in-arc CSR, which the call compacts and copies out -- rowptr (n + 1 offsets by head),
+ * tails and load hold arc_cap positions (SRT_E_RANGE when the graph has more essential arcs;
+ * *narcs receives the number). The call zeroes load, through and totals itself. */
+int srt_split_load_dense_device(int32_t n, int32_t ld, int32_t directed, const uint32_t* w,
+                                const uint32_t* lat, int32_t row0, int32_t nrows,
+                                const uint64_t* dem, size_t ldd, int64_t arc_cap, int32_t* rowptr,
+                                int32_t* tails, double* load, int64_t* narcs, double* through,
+                                uint64_t* totals, void* stream, srt_split_load_stats* stats);
+/* The split load of a demand on a host edge list: the arguments, demand conventions, choice of
+ * algorithm, chunks, front ends and refusals of srt_build_link_load (ndem < 0 uniform, else COO;
+ * one GPU; a graph whose distances need u64 rows: SRT_E_RANGE), and SRT_E_RANGE before any device
+ * work for a total demand of 2^53 or more. No route is computed: the pass reads the distance rows.
+ * use_shortest_path = 0: load(s -> t) = c(s, t), through = 0, on the host (SRT_E_INVALID unless
+ * the graph is complete). *out is freed with srt_split_load_free. */
+int srt_build_split_load(const srt_edges* g, const srt_build_opts* opts, int32_t nsrc,
+                         const int32_t* srcs, int64_t ndem, const int32_t* dsrc,
+                         const int32_t* dtgt, const uint64_t* dval, srt_split_load** out);
+void srt_split_load_free(srt_split_load* sl);
+
 /* ---- multi-GPU (one process per GPU; RCCL over xGMI) ----------------------------------- */
 typedef struct srt_comm srt_comm;
 /* 128-byte RCCL unique id, created on rank 0 and shared by the caller (e.g. torch.distributed). */

@@ -147,6 +147,14 @@ int32_t srt_topology_route_builds(Topology* top);
 int srt_topology_link_load(Topology* top, srt_link_load** out);
 /* srt_build_link_load calls this topology has made (diagnostic) */
 int32_t srt_topology_link_load_builds(Topology* top);
+/* ---- split load (splitload.hip): the same counters with every shortest-path tie split evenly --
+ * The same snapshot of the counters becomes the demand of srt_build_split_load: the expected
+ * traffic per arc and per vertex when every tied predecessor is drawn uniformly, where
+ * srt_topology_link_load charges the canonical route alone. Like it the call records no
+ * pair-order lookup, changes no counter (srt_topology_link_load_builds included), offers nothing
+ * to the runahead hook and does not touch the route rows. *out is freed with
+ * srt_split_load_free. */
+int srt_topology_split_load(Topology* top, srt_split_load** out);
 /* Graph facts established by validation (topology.c:659-716). */
 int32_t srt_topology_vertex_count(Topology* top);
 int64_t srt_topology_edge_count(Topology* top);

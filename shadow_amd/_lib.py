@@ -127,6 +127,32 @@ class LinkLoadStats(ctypes.Structure):
     ]
 
 
+class SplitLoad(ctypes.Structure):
+    _fields_ = [
+        ("narcs", ctypes.c_int64),
+        ("tail", ctypes.POINTER(ctypes.c_int32)),
+        ("head", ctypes.POINTER(ctypes.c_int32)),
+        ("load", ctypes.POINTER(ctypes.c_double)),
+        ("through", ctypes.POINTER(ctypes.c_double)),
+        ("routed", ctypes.c_uint64),
+        ("unrouted", ctypes.c_uint64),
+        ("self_demand", ctypes.c_uint64),
+        ("ms_tables", ctypes.c_double),
+        ("ms_split", ctypes.c_double),
+        ("tied_pairs", ctypes.c_int64),
+        ("forms", ctypes.c_int32),
+    ]
+
+
+class SplitLoadStats(ctypes.Structure):
+    _fields_ = [
+        ("ms_split", ctypes.c_double),
+        ("tied_pairs", ctypes.c_int64),
+        ("max_sweeps", ctypes.c_int32),
+        ("forms", ctypes.c_int32),
+    ]
+
+
 # (name, restype, argtypes) for every exported symbol of the C-ABI
 _VP, _I32, _I64, _U32, _U64, _D, _CP = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
                                          ctypes.c_uint32, ctypes.c_uint64, ctypes.c_double,
@@ -177,6 +203,14 @@ SIGNATURES = {
     "srt_envelope_dense_device": (ctypes.c_int, [_I32, _I32, _I32, _VP, _VP, _VP, _I32, _I32, _VP,
                                                   _VP, ctypes.c_size_t, _VP, _VP]),
     "srt_build_rel_envelope": (ctypes.c_int, [_VP, _VP, _I32, _VP, _VP, _VP, _VP]),
+    "srt_split_load_stage_max_n": (ctypes.c_int, [ctypes.c_int]),
+    "srt_split_load_rows_device": (ctypes.c_int, [_VP, _I32, _VP, _I32, _VP, ctypes.c_size_t, _VP,
+                                                   ctypes.c_size_t, _VP, _VP, _VP, _VP, _VP]),
+    "srt_split_load_dense_device": (ctypes.c_int, [_I32, _I32, _I32, _VP, _VP, _I32, _I32, _VP,
+                                                    ctypes.c_size_t, _I64, _VP, _VP, _VP, _VP, _VP,
+                                                    _VP, _VP, _VP]),
+    "srt_build_split_load": (ctypes.c_int, [_VP, _VP, _I32, _VP, _I64, _VP, _VP, _VP, _VP]),
+    "srt_split_load_free": (None, [_VP]),
     "srt_comm_unique_id": (ctypes.c_int, [_VP]),
     "srt_comm_init": (ctypes.c_int, [_VP, _I32, _I32, _I32, _VP]),
     "srt_comm_init_all": (ctypes.c_int, [_I32, _VP, _VP]),
@@ -239,6 +273,7 @@ SIGNATURES = {
     "srt_topology_route_builds": (_I32, [_VP]),
     "srt_topology_link_load": (ctypes.c_int, [_VP, _VP]),
     "srt_topology_link_load_builds": (_I32, [_VP]),
+    "srt_topology_split_load": (ctypes.c_int, [_VP, _VP]),
     "srt_topology_vertex_count": (_I32, [_VP]),
     "srt_topology_edge_count": (_I64, [_VP]),
     "srt_topology_is_directed": (ctypes.c_int, [_VP]),

@@ -2226,6 +2226,8 @@ struct route_source {
     int envelope;     /* set before the open: the envelope pass reads this source (ir, ms_ess_rel);
                        * a step then runs the route pass only where a route output is wanted */
     double ms_ess_rel;
+    int rows_only;    /* set before the open: the pass reads the distance rows and the CSR alone (the
+                       * split load); a step runs the route pass only where an output is wanted */
     int chunk;        /* rows a step */
     int32_t* dout[3]; /* pred, first, hops of the last step's rows (stride n; NULL: not asked) */
     int cnt;          /* ... how many, and their sources (NULL: the vertices from the step's r0) */
@@ -2321,7 +2323,7 @@ static int route_source_step(route_source* s, int r0) {
         TRY(sparse_chunk(s->sg, s->dverts, r0, s->cnt, s->dlat, s->drel, NULL, s->st, &bs));
         s->stats.ms_tables += bs.ms_total;
     }
-    if (!s->envelope || s->dout[0] || s->dout[1] || s->dout[2])
+    if (!(s->envelope || s->rows_only) || s->dout[0] || s->dout[1] || s->dout[2])
         TRY(srt_routes_rows_timed(n, s->cnt, s->srcs, r0, s->dense, s->dlat,
                                   (size_t)(s->dense ? s->ld : n), s->irp, s->icol, s->iw, s->dout[0],
                                   s->dout[1], s->dout[2], (size_t)n, s->st, &s->stats));
@@ -2682,6 +2684,56 @@ struct ll_demand {
     const uint64_t* val;
 };
 
+/* the demand arguments of `who` (srt_build_link_load's conventions) checked and taken into *dm;
+ * dverts and rowptr hold what dm points to for COO demands; *total: the demand summed (uniform:
+ * nsub * n) */
+static int ll_demand_parse(const char* who, int n, int32_t nsrc, const int32_t* srcs, int64_t ndem,
+                           const int32_t* dsrc, const int32_t* dtgt, const uint64_t* dval,
+                           ll_demand* dm, std::vector<int32_t>* dverts, std::vector<int64_t>* rowptr,
+                           uint64_t* total) {
+    *total = 0;
+    if (ndem < 0) {
+        if (check_verts(n, nsrc, srcs)) {
+            srt_set_error("%s: the sources must be 1..n strictly increasing vertex "
+                          "indices (or NULL with nsrc = n)", who);
+            return SRT_E_ARG;
+        }
+        dm->nsub = nsrc;
+        dm->verts = srcs;
+        *total = (uint64_t)nsrc * (uint64_t)n;
+        return SRT_OK;
+    }
+    if (srcs || (ndem > 0 && (!dsrc || !dtgt || !dval))) {
+        srt_set_error("%s: COO demands take their sources from dsrc (srcs must "
+                      "be NULL) and need all three arrays", who);
+        return SRT_E_ARG;
+    }
+    for (int64_t k = 0; k < ndem; k++) {
+        if (dsrc[k] < 0 || dsrc[k] >= n || dtgt[k] < 0 || dtgt[k] >= n ||
+            (k && dsrc[k] < dsrc[k - 1])) {
+            srt_set_error("%s: demand %lld: vertices within [0, %d), grouped by "
+                          "source in increasing order", who, (long long)k, n);
+            return SRT_E_ARG;
+        }
+        if (*total + dval[k] < *total) {
+            srt_set_error("%s: the total demand passes 2^64 - 1 at entry %lld", who, (long long)k);
+            return SRT_E_RANGE;
+        }
+        *total += dval[k];
+        if (!k || dsrc[k] != dsrc[k - 1]) {
+            dverts->push_back(dsrc[k]);
+            rowptr->push_back(k);
+        }
+    }
+    rowptr->push_back(ndem);
+    dm->nsub = (int32_t)dverts->size();
+    dm->verts = dm->nsub == n ? NULL : dverts->data(); /* n distinct sources: every vertex */
+    dm->rowptr = rowptr->data();
+    dm->tgt = dtgt;
+    dm->val = dval;
+    return SRT_OK;
+}
+
 /* the positions of a by-head CSR that carry load, as (tail, head, load) sorted by (tail, head) */
 static int link_load_collect(int n, const int32_t* irp, const int32_t* icol, const uint64_t* load,
                              srt_link_load* ll) {
@@ -2873,46 +2925,10 @@ extern "C" int srt_build_link_load(const srt_edges* g, const srt_build_opts* opt
     ll_demand dm = {0, NULL, NULL, NULL, NULL};
     std::vector<int32_t> dverts;
     std::vector<int64_t> rowptr;
-    if (ndem < 0) {
-        if (check_verts(n, nsrc, srcs)) {
-            srt_set_error("srt_build_link_load: the sources must be 1..n strictly increasing vertex "
-                          "indices (or NULL with nsrc = n)");
-            return SRT_E_ARG;
-        }
-        dm.nsub = nsrc;
-        dm.verts = srcs;
-    } else {
-        if (srcs || (ndem > 0 && (!dsrc || !dtgt || !dval))) {
-            srt_set_error("srt_build_link_load: COO demands take their sources from dsrc (srcs must "
-                          "be NULL) and need all three arrays");
-            return SRT_E_ARG;
-        }
-        uint64_t total = 0;
-        for (int64_t k = 0; k < ndem; k++) {
-            if (dsrc[k] < 0 || dsrc[k] >= n || dtgt[k] < 0 || dtgt[k] >= n ||
-                (k && dsrc[k] < dsrc[k - 1])) {
-                srt_set_error("srt_build_link_load: demand %lld: vertices within [0, %d), grouped by "
-                              "source in increasing order", (long long)k, n);
-                return SRT_E_ARG;
-            }
-            if (total + dval[k] < total) {
-                srt_set_error("srt_build_link_load: the total demand passes 2^64 - 1 at entry %lld",
-                              (long long)k);
-                return SRT_E_RANGE;
-            }
-            total += dval[k];
-            if (!k || dsrc[k] != dsrc[k - 1]) {
-                dverts.push_back(dsrc[k]);
-                rowptr.push_back(k);
-            }
-        }
-        rowptr.push_back(ndem);
-        dm.nsub = (int32_t)dverts.size();
-        dm.verts = dm.nsub == n ? NULL : dverts.data(); /* n distinct sources: every vertex */
-        dm.rowptr = rowptr.data();
-        dm.tgt = dtgt;
-        dm.val = dval;
-    }
+    uint64_t total = 0;
+    const int drc = ll_demand_parse("srt_build_link_load", n, nsrc, srcs, ndem, dsrc, dtgt, dval, &dm,
+                                    &dverts, &rowptr, &total);
+    if (drc) return drc;
     srt_link_load* ll = link_load_new(n, 0);
     if (!ll) {
         srt_set_error("srt_build_link_load: out of memory");
@@ -2946,5 +2962,321 @@ extern "C" int srt_build_link_load(const srt_edges* g, const srt_build_opts* opt
         return rc;
     }
     *out = ll;
+    return SRT_OK;
+}
+
+/* ------------------------------------------------------------------------------------------ */
+/* Split load (splitload.hip): the distance rows of the route source, then the load with every  */
+/* tie split evenly over the chunk's demand rows; no route output is wanted, so its steps skip  */
+/* the route pass.                                                                              */
+/* ------------------------------------------------------------------------------------------ */
+extern "C" int srt_split_load_rows_device(const srt_sparse_graph* g, int32_t nsrc,
+                                          const int32_t* srcs, int32_t src_begin,
+                                          const uint32_t* lat_rows, size_t ldl, const uint64_t* dem,
+                                          size_t ldd, double* load, double* through,
+                                          uint64_t* totals, void* stream,
+                                          srt_split_load_stats* stats) {
+    if (!g || nsrc < 1 || !lat_rows || ldl < (size_t)g->n ||
+        (!srcs && (src_begin < 0 || (int64_t)src_begin + nsrc > g->n))) {
+        srt_set_error("srt_split_load_rows_device: bad arguments");
+        return SRT_E_ARG;
+    }
+    if (g->wide) {
+        srt_set_error("srt_split_load_rows_device: shortest-path latencies may pass the u32 range; "
+                      "the split-load pass reads u32 rows only");
+        return SRT_E_RANGE;
+    }
+    srt_split_load_stats local;
+    memset(&local, 0, sizeof(local));
+    const int rc = srt_split_load_rows(g->n, nsrc, srcs, src_begin, 0, lat_rows, ldl, dem, ldd,
+                                       g->irp, g->icol, g->iw, load, through, totals,
+                                       (hipStream_t)stream, &local);
+    if (!rc && stats) *stats = local;
+    return rc;
+}
+
+extern "C" int srt_split_load_dense_device(int32_t n, int32_t ld, int32_t directed,
+                                           const uint32_t* w, const uint32_t* lat, int32_t row0,
+                                           int32_t nrows, const uint64_t* dem, size_t ldd,
+                                           int64_t arc_cap, int32_t* rowptr, int32_t* tails,
+                                           double* load, int64_t* narcs, double* through,
+                                           uint64_t* totals, void* stream,
+                                           srt_split_load_stats* stats) {
+    if (n < 1 || ld < n || !w || !lat || row0 < 0 || nrows < 1 || (int64_t)row0 + nrows > n ||
+        arc_cap < 0 || !dem || !rowptr || !tails || !load || !through || !totals) {
+        srt_set_error("srt_split_load_dense_device: bad arguments (n = %d, ld = %d, rows [%d, %d))", n,
+                      ld, row0, row0 + nrows);
+        return SRT_E_ARG;
+    }
+    if (n > SRT_DENSE_MAX_N) {
+        srt_set_error("srt_split_load_dense_device: n = %d beyond the dense limit %d", n,
+                      SRT_DENSE_MAX_N);
+        return SRT_E_RANGE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    srt_split_load_stats local;
+    memset(&local, 0, sizeof(local));
+    int32_t *irp = NULL, *icol = NULL;
+    uint32_t* iw = NULL;
+    int64_t arcs = 0;
+    double ms_ess = 0;
+    int rc = srt_routes_ess_build(n, ld, directed, w, lat, st, &irp, &icol, &iw, &arcs, &ms_ess);
+    if (!rc && narcs) *narcs = arcs;
+    if (!rc && arcs > arc_cap) {
+        srt_set_error("srt_split_load_dense_device: %lld essential arcs, room for %lld",
+                      (long long)arcs, (long long)arc_cap);
+        rc = SRT_E_RANGE;
+    }
+    if (!rc) {
+        TRYHIP(hipMemcpyAsync(rowptr, irp, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        TRYHIP(hipMemcpyAsync(tails, icol, (size_t)arcs * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        TRYHIP(hipMemsetAsync(load, 0, (size_t)arcs * sizeof(double), st));
+        TRYHIP(hipMemsetAsync(through, 0, (size_t)n * sizeof(double), st));
+        TRYHIP(hipMemsetAsync(totals, 0, 3 * sizeof(uint64_t), st));
+        rc = srt_split_load_rows(n, nrows, NULL, row0, 0, lat + (size_t)row0 * ld, (size_t)ld, dem, ldd,
+                                 irp, icol, iw, load, through, totals, st, &local);
+    }
+out:
+    srt_routes_ess_free(irp, icol, iw, st);
+    if (!rc && stats) *stats = local;
+    return rc;
+}
+
+extern "C" void srt_split_load_free(srt_split_load* sl) {
+    if (!sl) return;
+    free(sl->tail);
+    free(sl->head);
+    free(sl->load);
+    free(sl->through);
+    free(sl);
+}
+
+/* the arcs (tail, head, load) as the result's, by (tail, head): k of them, which may be 0 */
+static int split_load_set_arcs(srt_split_load* sl, const int32_t* tail, const int32_t* head,
+                               const double* load, size_t k) {
+    const size_t room = k ? k : 1;
+    free(sl->tail);
+    free(sl->head);
+    free(sl->load);
+    sl->tail = (int32_t*)malloc(room * sizeof(int32_t));
+    sl->head = (int32_t*)malloc(room * sizeof(int32_t));
+    sl->load = (double*)malloc(room * sizeof(double));
+    if (!sl->tail || !sl->head || !sl->load) {
+        srt_set_error("srt_build_split_load: out of memory for %zu arcs", k);
+        return SRT_E_NOMEM;
+    }
+    if (k) {
+        memcpy(sl->tail, tail, k * sizeof(int32_t));
+        memcpy(sl->head, head, k * sizeof(int32_t));
+        memcpy(sl->load, load, k * sizeof(double));
+    }
+    sl->narcs = (int64_t)k;
+    return SRT_OK;
+}
+
+/* the positions of a by-head CSR that carry load, as the result's arcs */
+static int split_load_collect(int n, const int32_t* irp, const int32_t* icol, const double* load,
+                              srt_split_load* sl) {
+    const int64_t na = irp[n];
+    std::vector<int64_t> start((size_t)n + 1, 0);
+    int64_t cnt = 0;
+    for (int64_t k = 0; k < na; k++)
+        if (load[k] > 0.0) {
+            start[(size_t)icol[k] + 1]++;
+            cnt++;
+        }
+    for (int v = 0; v < n; v++) start[(size_t)v + 1] += start[v];
+    std::vector<int32_t> tail((size_t)cnt), head((size_t)cnt);
+    std::vector<double> ld((size_t)cnt);
+    /* heads ascend in the outer loop, so each tail's arcs come out by head */
+    for (int t = 0; t < n; t++)
+        for (int64_t k = irp[t]; k < irp[t + 1]; k++)
+            if (load[k] > 0.0) {
+                const int64_t o = start[icol[k]]++;
+                tail[o] = icol[k];
+                head[o] = t;
+                ld[o] = load[k];
+            }
+    return split_load_set_arcs(sl, tail.data(), head.data(), ld.data(), (size_t)cnt);
+}
+
+/* one GPU: the split-load pass over every chunk of the route source's distance rows and the
+ * chunk's demand rows, which are built on the device */
+static int split_load_one(const srt_canon* c, const srt_build_opts* opts, int algo,
+                          const ll_demand* dm, srt_split_load* sl) {
+    const int n = c->n;
+    const int nsub = dm->nsub;
+    route_source src = {};
+    dbufs B;
+    B.k = 0;
+    int32_t* dtgt = NULL;
+    int64_t* drowptr = NULL;
+    uint64_t *ddem = NULL, *dval = NULL, *dtot = NULL;
+    double *dload = NULL, *dthrough = NULL;
+    int64_t narcs = 0, max_ent = 0;
+    uint64_t htot[3] = {0, 0, 0};
+    const bool none[3] = {false, false, false};
+    srt_split_load_stats ss;
+    hipStream_t st = NULL;
+    std::vector<int32_t> hirp, hicol;
+    std::vector<double> hload;
+    std::vector<int64_t> rel_rowptr;
+    int rc = SRT_OK;
+    memset(&ss, 0, sizeof(ss));
+    src.rows_only = 1;
+    TRY(route_source_open(&src, c, opts, algo, nsub, dm->verts));
+    st = src.st;
+    narcs = src.narcs;
+    /* beside the source's rows: the load itself, and a u64 demand row per source row */
+    TRY(route_source_chunks(&src, (size_t)narcs * 8, (size_t)n * 8, none));
+    TRY(dalloc(&B, (void**)&ddem, (size_t)src.chunk * n * sizeof(uint64_t)));
+    TRY(dalloc(&B, (void**)&dload, (size_t)narcs * sizeof(double)));
+    TRY(dalloc(&B, (void**)&dthrough, (size_t)n * sizeof(double)));
+    TRY(dalloc(&B, (void**)&dtot, 3 * sizeof(uint64_t)));
+    TRYHIP(hipMemsetAsync(dload, 0, (size_t)narcs * sizeof(double), st));
+    TRYHIP(hipMemsetAsync(dthrough, 0, (size_t)n * sizeof(double), st));
+    TRYHIP(hipMemsetAsync(dtot, 0, 3 * sizeof(uint64_t), st));
+    if (dm->rowptr) { /* room for the COO entries of the largest chunk */
+        for (int r0 = 0; r0 < nsub; r0 += src.chunk) {
+            const int r1 = r0 + src.chunk < nsub ? r0 + src.chunk : nsub;
+            const int64_t e = dm->rowptr[r1] - dm->rowptr[r0];
+            max_ent = e > max_ent ? e : max_ent;
+        }
+        TRY(dalloc(&B, (void**)&drowptr, ((size_t)src.chunk + 1) * sizeof(int64_t)));
+        TRY(dalloc(&B, (void**)&dtgt, (size_t)max_ent * sizeof(int32_t)));
+        TRY(dalloc(&B, (void**)&dval, (size_t)max_ent * sizeof(uint64_t)));
+        rel_rowptr.resize((size_t)src.chunk + 1);
+    }
+    for (int r0 = 0; r0 < nsub; r0 += src.chunk) {
+        TRY(route_source_step(&src, r0));
+        const int cnt = src.cnt;
+        if (dm->rowptr) { /* the chunk's entries, their row offsets re-based to its first row */
+            const int64_t e0 = dm->rowptr[r0], ne = dm->rowptr[r0 + cnt] - e0;
+            for (int i = 0; i <= cnt; i++) rel_rowptr[i] = dm->rowptr[r0 + i] - e0;
+            TRYHIP(hipMemcpyAsync(drowptr, rel_rowptr.data(), ((size_t)cnt + 1) * sizeof(int64_t),
+                                  hipMemcpyHostToDevice, st));
+            if (ne > 0) {
+                TRYHIP(hipMemcpyAsync(dtgt, dm->tgt + e0, (size_t)ne * sizeof(int32_t),
+                                      hipMemcpyHostToDevice, st));
+                TRYHIP(hipMemcpyAsync(dval, dm->val + e0, (size_t)ne * sizeof(uint64_t),
+                                      hipMemcpyHostToDevice, st));
+            }
+            TRYHIP(hipStreamSynchronize(st)); /* rel_rowptr is reused by the next chunk */
+        }
+        TRY(srt_link_load_demand_rows(n, cnt, drowptr, dtgt, dval, ddem, (size_t)n, st));
+        TRY(srt_split_load_rows(n, cnt, src.srcs, r0, src.dense, src.dlat,
+                                src.dense ? (size_t)src.ld : (size_t)n, ddem, (size_t)n, src.irp,
+                                src.icol, src.iw, dload, dthrough, dtot, st, &ss));
+    }
+    hirp.resize((size_t)n + 1);
+    hicol.resize((size_t)(narcs > 0 ? narcs : 1));
+    hload.resize((size_t)(narcs > 0 ? narcs : 1));
+    TRYHIP(hipMemcpyAsync(hirp.data(), src.irp, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (narcs > 0) {
+        TRYHIP(hipMemcpyAsync(hicol.data(), src.icol, (size_t)narcs * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        TRYHIP(hipMemcpyAsync(hload.data(), dload, (size_t)narcs * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    TRYHIP(hipMemcpyAsync(sl->through, dthrough, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+    TRYHIP(hipMemcpyAsync(htot, dtot, sizeof(htot), hipMemcpyDeviceToHost, st));
+    TRYHIP(hipStreamSynchronize(st));
+    TRY(split_load_collect(n, hirp.data(), hicol.data(), hload.data(), sl));
+    sl->routed = htot[0];
+    sl->unrouted = htot[1];
+    sl->self_demand = htot[2];
+    sl->ms_tables = src.stats.ms_tables;
+    sl->ms_split = ss.ms_split;
+    sl->tied_pairs = ss.tied_pairs;
+    sl->forms = ss.forms;
+out:
+    route_source_close(&src);
+    dfree(&B);
+    return rc;
+}
+
+/* direct mode (topology.c:1816-1858): every pair is its own edge, so load(s -> t) = c(s, t) */
+static int split_load_direct(const srt_edges* g, const ll_demand* dm, srt_split_load* sl) {
+    const int n = g->n;
+    std::vector<int32_t> tail, head;
+    std::vector<double> load;
+    std::vector<uint64_t> row;
+    if (dm->rowptr) row.assign((size_t)n, 0);
+    for (int32_t i = 0; i < dm->nsub; i++) {
+        const int32_t s = dm->verts ? dm->verts[i] : i;
+        if (dm->rowptr)
+            for (int64_t k = dm->rowptr[i]; k < dm->rowptr[i + 1]; k++) row[dm->tgt[k]] += dm->val[k];
+        for (int32_t t = 0; t < n; t++) {
+            const uint64_t cst = dm->rowptr ? row[t] : 1;
+            if (dm->rowptr) row[t] = 0;
+            if (!cst) continue;
+            if (t == s) {
+                sl->self_demand += cst;
+                continue;
+            }
+            sl->routed += cst;
+            tail.push_back(s);
+            head.push_back(t);
+            load.push_back((double)cst);
+        }
+    }
+    return split_load_set_arcs(sl, tail.data(), head.data(), load.data(), tail.size());
+}
+
+extern "C" int srt_build_split_load(const srt_edges* g, const srt_build_opts* opts, int32_t nsrc,
+                                    const int32_t* srcs, int64_t ndem, const int32_t* dsrc,
+                                    const int32_t* dtgt, const uint64_t* dval,
+                                    srt_split_load** out) {
+    if (out) *out = NULL;
+    if (!g || g->n <= 0 || !out) {
+        srt_set_error("srt_build_split_load: null argument");
+        return SRT_E_ARG;
+    }
+    last_row_chunks.store(0, std::memory_order_relaxed);
+    const int n = g->n;
+    ll_demand dm = {0, NULL, NULL, NULL, NULL};
+    std::vector<int32_t> dverts;
+    std::vector<int64_t> rowptr;
+    uint64_t total = 0;
+    int rc = ll_demand_parse("srt_build_split_load", n, nsrc, srcs, ndem, dsrc, dtgt, dval, &dm,
+                             &dverts, &rowptr, &total);
+    if (rc) return rc;
+    if (total >= (uint64_t)1 << 53) { /* every c and every total then converts to f64 exactly */
+        srt_set_error("srt_build_split_load: a total demand of %llu (2^53 or more) is not exact in "
+                      "f64", (unsigned long long)total);
+        return SRT_E_RANGE;
+    }
+    srt_split_load* sl = (srt_split_load*)calloc(1, sizeof(srt_split_load));
+    if (sl) sl->through = (double*)calloc((size_t)n, sizeof(double));
+    if (!sl || !sl->through) {
+        srt_split_load_free(sl);
+        srt_set_error("srt_build_split_load: out of memory");
+        return SRT_E_NOMEM;
+    }
+    const int use_sp = opts ? opts->use_shortest_path : 1;
+    if (!use_sp) {
+        int32_t* const none[3] = {NULL, NULL, NULL};
+        rc = routes_direct(g, 0, NULL, none); /* the completeness check and its error */
+        if (!rc) rc = split_load_direct(g, &dm, sl);
+    } else if (dm.nsub == 0) {
+        rc = split_load_set_arcs(sl, NULL, NULL, NULL, 0); /* no demand: nothing to route */
+    } else if (srt_device_count() < 1) {
+        srt_set_error("srt_build_split_load: no HIP device");
+        rc = SRT_E_DEVICE;
+    } else {
+        rc = with_canon(g, opts, 1, [&](const srt_canon* c, int algo, double) {
+            if (c->wide) {
+                srt_set_error("srt_build_split_load: shortest-path latencies may pass the u32 range "
+                              "(bound %llu quanta of %llu ns); the split-load pass reads u32 rows "
+                              "only", (unsigned long long)c->dist_bound,
+                              (unsigned long long)c->quantum_ns);
+                return (int)SRT_E_RANGE;
+            }
+            return split_load_one(c, opts, algo, &dm, sl);
+        });
+    }
+    if (rc) {
+        srt_split_load_free(sl);
+        return rc;
+    }
+    *out = sl;
     return SRT_OK;
 }

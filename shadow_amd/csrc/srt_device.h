@@ -355,6 +355,16 @@ int srt_envelope_rows(int n, int nrows, const int32_t* srcs, int src_begin, int 
  * returns it); *ms += the gather's HIP-event time */
 int srt_envelope_ess_rel(int n, int ld, int64_t arcs, const int32_t* irp, const int32_t* icol,
                          const double* r, hipStream_t st, double** ir, double* ms);
+/* splitload.hip: the load with every tie split evenly, over nrows distance rows (rows, sources and
+ * strides as srt_routes_rows) and u64 demand rows (stride ldc) against an in-arc CSR: ADDS into
+ * load (one f64 word per CSR position), through (n f64) and totals (routed, unrouted, self). Adds
+ * the HIP-event time, the tied pairs, the sweeps and the staging forms to *stats; returns after
+ * the stream */
+int srt_split_load_rows(int n, int nrows, const int32_t* srcs, int src_begin, int by_src,
+                        const uint32_t* D, size_t ldd, const uint64_t* dem, size_t ldc,
+                        const int32_t* irp, const int32_t* icol, const uint32_t* iw, double* load,
+                        double* through, uint64_t* totals, hipStream_t st,
+                        srt_split_load_stats* stats);
 /* collectives: all-gather of equal byte blocks, rank q's block at buf + q * bytes */
 int srt_coll_allgather(const srt_comm* c, void* buf, size_t bytes, hipStream_t st);
 

@@ -1833,15 +1833,8 @@ int64_t srt_topology_route_string_ip(Topology* t, uint32_t srcIp, uint32_t dstIp
     return len;
 }
 
-/* ---- link load: the packet counters charged to the arcs of their routes -------------------- *
- * A counter belongs to the served Path (from, to) (path.c:57-59), so its packets are charged to
- * the arcs of route(from, to) in that direction, whichever way the pair was looked up. The
- * counter pages are read with relaxed loads into COO demands, sources ascending as the pages are
- * walked; self paths land in self_demand. Like a route query this records no pair-order lookup,
- * changes no counter, offers nothing to the runahead hook and leaves the route rows alone. */
-int srt_topology_link_load(Topology* t, srt_link_load** out) {
-    if (out) *out = NULL;
-    if (!magic_ok(t) || !out) return SRT_E_ARG;
+/* the non-zero counters as COO demands (malloc'd arrays the caller frees, *k entries) */
+static int counters_coo(Topology* t, int32_t** psrc, int32_t** ptgt, uint64_t** pval, int64_t* pk) {
     cntmap_t* m = &t->counters;
     int64_t cap = 1024, k = 0;
     int32_t* dsrc = (int32_t*)malloc((size_t)cap * sizeof(int32_t));
@@ -1877,9 +1870,28 @@ int srt_topology_link_load(Topology* t, srt_link_load** out) {
             }
         }
     }
-    if (rc) {
-        srt_set_error("out of memory for the packet-counter snapshot");
-    } else {
+    if (rc) srt_set_error("out of memory for the packet-counter snapshot");
+    *psrc = dsrc;
+    *ptgt = dtgt;
+    *pval = dval;
+    *pk = k;
+    return rc;
+}
+
+/* ---- link load: the packet counters charged to the arcs of their routes -------------------- *
+ * A counter belongs to the served Path (from, to) (path.c:57-59), so its packets are charged to
+ * the arcs of route(from, to) in that direction, whichever way the pair was looked up. The
+ * counter pages are read with relaxed loads into COO demands, sources ascending as the pages are
+ * walked; self paths land in self_demand. Like a route query this records no pair-order lookup,
+ * changes no counter, offers nothing to the runahead hook and leaves the route rows alone. */
+int srt_topology_link_load(Topology* t, srt_link_load** out) {
+    if (out) *out = NULL;
+    if (!magic_ok(t) || !out) return SRT_E_ARG;
+    int32_t *dsrc = NULL, *dtgt = NULL;
+    uint64_t* dval = NULL;
+    int64_t k = 0;
+    int rc = counters_coo(t, &dsrc, &dtgt, &dval, &k);
+    if (!rc) {
         srt_edges e;
         srt_topology_edges(t, &e);
         srt_build_opts o = t->opts;
@@ -1887,6 +1899,28 @@ int srt_topology_link_load(Topology* t, srt_link_load** out) {
         rc = srt_build_link_load(&e, &o, 0, NULL, k, dsrc, dtgt, dval, out);
         atomic_fetch_add(&t->link_load_builds, 1);
         if (rc) srt_log(SRT_LOG_ERROR, "link-load build failed (%d): %s", rc, srt_last_error());
+    }
+    free(dsrc);
+    free(dtgt);
+    free(dval);
+    return rc;
+}
+
+/* the same snapshot with every tie split evenly (splitload.hip); no counter of the topology moves */
+int srt_topology_split_load(Topology* t, srt_split_load** out) {
+    if (out) *out = NULL;
+    if (!magic_ok(t) || !out) return SRT_E_ARG;
+    int32_t *dsrc = NULL, *dtgt = NULL;
+    uint64_t* dval = NULL;
+    int64_t k = 0;
+    int rc = counters_coo(t, &dsrc, &dtgt, &dval, &k);
+    if (!rc) {
+        srt_edges e;
+        srt_topology_edges(t, &e);
+        srt_build_opts o = t->opts;
+        o.use_shortest_path = t->use_shortest_path;
+        rc = srt_build_split_load(&e, &o, 0, NULL, k, dsrc, dtgt, dval, out);
+        if (rc) srt_log(SRT_LOG_ERROR, "split-load build failed (%d): %s", rc, srt_last_error());
     }
     free(dsrc);
     free(dtgt);

@@ -24,7 +24,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (BuildOpts, BuildStats, Edges, EnvelopeStats, LinkLoad, LinkLoadStats, RouteStats,
-                   check, lib)
+                   SplitLoad, check, lib)
 
 
 def ip_to_net(ip) -> int:
@@ -296,6 +296,13 @@ class Topology:
     def link_load_builds(self) -> int:
         return lib().srt_topology_link_load_builds(self._h)
 
+    def split_load(self):
+        """srt_topology_split_load: the packet counters with every shortest-path tie split evenly ->
+        (tail, head, load, through, info) as build_split_load returns them."""
+        out = ctypes.POINTER(SplitLoad)()
+        check(lib().srt_topology_split_load(self._h, ctypes.byref(out)), "srt_topology_split_load")
+        return _take_split_load(out, self.n)
+
 
 MIN_HOOK = ctypes.CFUNCTYPE(None, ctypes.c_double)
 
@@ -455,14 +462,9 @@ def demand_coo(demand, sources, n):
     return ss[r].astype(np.int32), t.astype(np.int32), d[r, t].astype(np.uint64)
 
 
-def build_link_load(n, directed, src, dst, lat_ns, loss, sources=None, demand=None,
-                    use_shortest_path=True, device=0, algo=_lib.ALGO_AUTO):
-    """srt_build_link_load on host arrays -> (tail, head, load, through, stats): the arcs that carry
-    load by (tail, head), the u64 load of each, the u64 transit traffic of every vertex, and the
-    totals, times, max_hops and forms (LinkLoadInfo).
-    demand: None -- 1 from every source of `sources` (strictly increasing; None = every vertex)
-    to every vertex; a dense [k, n] array (row i = sources[i]); or a COO triple (dsrc, dtgt, dval)
-    grouped by source in increasing order (duplicates add; `sources` must be None)."""
+def _build_load(fn, what, out, n, directed, src, dst, lat_ns, loss, sources, demand,
+                use_shortest_path, device, algo):
+    """The call of srt_build_link_load or srt_build_split_load (same arguments) into `out`."""
     src = np.ascontiguousarray(src, np.int32)
     dst = np.ascontiguousarray(dst, np.int32)
     lat_ns = np.ascontiguousarray(lat_ns, np.int64)
@@ -470,12 +472,10 @@ def build_link_load(n, directed, src, dst, lat_ns, loss, sources=None, demand=No
     e = Edges(n, int(bool(directed)), len(src), src.ctypes.data, dst.ctypes.data,
               lat_ns.ctypes.data, loss.ctypes.data)
     o = BuildOpts(device, algo, int(bool(use_shortest_path)), 0)
-    out = ctypes.POINTER(LinkLoad)()
     if demand is None:
         ss = None if sources is None else np.ascontiguousarray(sources, np.int32)
-        rc = lib().srt_build_link_load(ctypes.byref(e), ctypes.byref(o), n if ss is None else len(ss),
-                                       None if ss is None else ss.ctypes.data, -1, None, None, None,
-                                       ctypes.byref(out))
+        rc = fn(ctypes.byref(e), ctypes.byref(o), n if ss is None else len(ss),
+                None if ss is None else ss.ctypes.data, -1, None, None, None, ctypes.byref(out))
     else:
         if isinstance(demand, tuple):
             if sources is not None:
@@ -488,11 +488,58 @@ def build_link_load(n, directed, src, dst, lat_ns, loss, sources=None, demand=No
         dval = np.ascontiguousarray(dval, np.uint64)
         if not len(dsrc) == len(dtgt) == len(dval):
             raise ValueError("the COO arrays differ in length")
-        rc = lib().srt_build_link_load(ctypes.byref(e), ctypes.byref(o), 0, None, len(dsrc),
-                                       dsrc.ctypes.data, dtgt.ctypes.data, dval.ctypes.data,
-                                       ctypes.byref(out))
-    check(rc, "srt_build_link_load")
+        rc = fn(ctypes.byref(e), ctypes.byref(o), 0, None, len(dsrc), dsrc.ctypes.data,
+                dtgt.ctypes.data, dval.ctypes.data, ctypes.byref(out))
+    check(rc, what)
+
+
+def build_link_load(n, directed, src, dst, lat_ns, loss, sources=None, demand=None,
+                    use_shortest_path=True, device=0, algo=_lib.ALGO_AUTO):
+    """srt_build_link_load on host arrays -> (tail, head, load, through, stats): the arcs that carry
+    load by (tail, head), the u64 load of each, the u64 transit traffic of every vertex, and the
+    totals, times, max_hops and forms (LinkLoadInfo).
+    demand: None -- 1 from every source of `sources` (strictly increasing; None = every vertex)
+    to every vertex; a dense [k, n] array (row i = sources[i]); or a COO triple (dsrc, dtgt, dval)
+    grouped by source in increasing order (duplicates add; `sources` must be None)."""
+    out = ctypes.POINTER(LinkLoad)()
+    _build_load(lib().srt_build_link_load, "srt_build_link_load", out, n, directed, src, dst, lat_ns,
+                loss, sources, demand, use_shortest_path, device, algo)
     return _take_link_load(out, n)
+
+
+class SplitLoadInfo:
+    """The scalar fields of srt_split_load."""
+
+    def __init__(self, sl):
+        for name in ("routed", "unrouted", "self_demand", "ms_tables", "ms_split", "forms"):
+            setattr(self, name, getattr(sl, name))
+        self.narcs = int(sl.narcs)
+        self.tied_pairs = int(sl.tied_pairs)
+
+
+def _take_split_load(out, n):
+    """(tail int32 [k], head int32 [k], load f64 [k], through f64 [n], SplitLoadInfo) copied out of
+    an srt_split_load, which is freed."""
+    sl = out.contents
+    k = int(sl.narcs)
+    arr = lambda p, m, dt: (np.ctypeslib.as_array(p, (m,)).astype(dt) if m else np.zeros(0, dt))
+    res = (arr(sl.tail, k, np.int32), arr(sl.head, k, np.int32), arr(sl.load, k, np.float64),
+           arr(sl.through, n, np.float64), SplitLoadInfo(sl))
+    lib().srt_split_load_free(out)
+    return res
+
+
+def build_split_load(n, directed, src, dst, lat_ns, loss, sources=None, demand=None,
+                     use_shortest_path=True, device=0, algo=_lib.ALGO_AUTO):
+    """srt_build_split_load on host arrays -> (tail, head, load, through, info): the link load with
+    every shortest-path tie split evenly -- the arcs with load > 0 by (tail, head), the f64 expected
+    load of each, the f64 expected transit traffic of every vertex, and the exact u64 totals, the
+    times, tied_pairs and forms (SplitLoadInfo). `demand` exactly as build_link_load takes it; a
+    total of 2^53 or more is refused."""
+    out = ctypes.POINTER(SplitLoad)()
+    _build_load(lib().srt_build_split_load, "srt_build_split_load", out, n, directed, src, dst,
+                lat_ns, loss, sources, demand, use_shortest_path, device, algo)
+    return _take_split_load(out, n)
 
 
 class SparseGraph:
@@ -581,6 +628,22 @@ class SparseGraph:
                                               ctypes.c_void_p(load_ptr), ctypes.c_void_p(through_ptr),
                                               ctypes.c_void_p(totals_ptr), ctypes.c_void_p(stream), st),
               "srt_link_load_rows_device")
+
+    def split_load_rows(self, lat_ptr, nsrc, dem_ptr, load_ptr, through_ptr, totals_ptr,
+                        srcs_ptr=None, src_begin=0, ldl=None, ldd=None, stream=None, stats=None):
+        """srt_split_load_rows_device over device pointers: adds the rows' split load into load
+        (arcs f64, indexed as in_arcs says), through (n f64) and totals (3 u64), which the caller
+        zeroes; row i of lat (stride ldl, default n) and of the u64 demand rows (stride ldd,
+        default n) belongs to srcs[i], or src_begin + i without a source list."""
+        st = ctypes.byref(stats) if stats is not None else None
+        check(lib().srt_split_load_rows_device(self._h, int(nsrc), ctypes.c_void_p(srcs_ptr),
+                                               int(src_begin), ctypes.c_void_p(lat_ptr),
+                                               self.n if ldl is None else int(ldl),
+                                               ctypes.c_void_p(dem_ptr),
+                                               self.n if ldd is None else int(ldd),
+                                               ctypes.c_void_p(load_ptr), ctypes.c_void_p(through_ptr),
+                                               ctypes.c_void_p(totals_ptr), ctypes.c_void_p(stream), st),
+              "srt_split_load_rows_device")
 
     def free(self):
         if getattr(self, "_h", None):
