@@ -2175,37 +2175,50 @@ extern "C" int srt_build_tables_multi(const srt_edges* g, const srt_build_opts* 
 /* the route pass over them -- never a builder's internal predecessors, so the pass stays a     */
 /* check on the builders.                                                                       */
 /* ------------------------------------------------------------------------------------------ */
+
+/* what the srt_*_rows_device wrappers of the passes that read distance rows check alike */
+static int rows_device_check(const char* who, const char* pass, const srt_sparse_graph* g,
+                             int32_t nsrc, const int32_t* srcs, int32_t src_begin,
+                             const uint32_t* lat_rows, size_t ldl) {
+    if (!g || nsrc < 1 || !lat_rows || ldl < (size_t)g->n ||
+        (!srcs && (src_begin < 0 || (int64_t)src_begin + nsrc > g->n))) {
+        srt_set_error("%s: bad arguments", who);
+        return SRT_E_ARG;
+    }
+    if (g->wide) {
+        srt_set_error("%s: shortest-path latencies may pass the u32 range; the %s reads u32 rows "
+                      "only", who, pass);
+        return SRT_E_RANGE;
+    }
+    return SRT_OK;
+}
+
 extern "C" int srt_routes_rows_device(const srt_sparse_graph* g, int32_t nsrc, const int32_t* srcs,
                                       int32_t src_begin, const uint32_t* lat_rows, size_t ldl,
                                       int32_t* pred, int32_t* first, int32_t* hops, size_t ldo,
                                       void* stream, srt_route_stats* stats) {
-    if (!g || nsrc < 1 || !lat_rows || ldl < (size_t)g->n ||
-        (!srcs && (src_begin < 0 || (int64_t)src_begin + nsrc > g->n))) {
-        srt_set_error("srt_routes_rows_device: bad arguments");
-        return SRT_E_ARG;
-    }
-    if (g->wide) {
-        srt_set_error("srt_routes_rows_device: shortest-path latencies may pass the u32 range; the "
-                      "route pass reads u32 rows only");
-        return SRT_E_RANGE;
-    }
-    srt_route_stats local;
-    memset(&local, 0, sizeof(local));
-    const int rc = srt_routes_rows_timed(g->n, nsrc, srcs, src_begin, 0, lat_rows, ldl, g->irp,
-                                         g->icol, g->iw, pred, first, hops, ldo,
-                                         (hipStream_t)stream, &local);
+    int rc = rows_device_check("srt_routes_rows_device", "route pass", g, nsrc, srcs, src_begin,
+                               lat_rows, ldl);
+    if (rc) return rc;
+    srt_route_stats local = {};
+    rc = srt_routes_rows_timed(g->n, nsrc, srcs, src_begin, 0, lat_rows, ldl, g->irp, g->icol, g->iw,
+                               pred, first, hops, ldo, (hipStream_t)stream, &local);
     if (!rc && stats) *stats = local;
     return rc;
 }
 
-/* The route rows of the sources verts (NULL: every vertex) on one GPU, a chunk at a time, for the
- * route export, the link load and the reliability envelope (which takes the distance rows and
- * the in-arc CSR alone: see `envelope`). route_source_open puts the distances' origin on the device (the
- * dense tables and their essential in-lists, or the sparse graph); route_source_chunks sizes the
- * chunk from the memory free at that point and allocates its rows; route_source_step computes the
- * rows of one chunk; route_source_close releases everything (after a failed open too). Start from
- * a zeroed struct. */
+/* The distance rows of the sources verts (NULL: every vertex) on one GPU, a chunk at a time, and
+ * what the pass behind them needs besides (set before the open): the route pass over each chunk,
+ * with the outputs it keeps, and the arcs' reliabilities. route_source_open puts the distances'
+ * origin on the device (the dense tables and their essential in-lists, or the sparse graph);
+ * route_source_chunks sizes the chunk from the memory free at that point and allocates its rows;
+ * route_source_step computes the rows of one chunk; route_source_close releases everything (after
+ * a failed open too). Start from a zeroed struct. */
 struct route_source {
+    /* the needs, set before the open */
+    bool routes;  /* a step runs the route pass (the route export: even with no output kept) */
+    bool want[3]; /* ... and keeps its pred, first, hops rows in dout */
+    bool want_ir; /* the arcs' reliabilities ir (dense: gathered at the open, ms_ess_rel) */
     int n, nsub, dense, ld;
     hipStream_t st;
     dbufs B;
@@ -2216,31 +2229,30 @@ struct route_source {
     double* dr;           /* dense: the ld x ld arc reliabilities */
     int32_t *ess_rp, *ess_col; /* dense: the essential in-lists (srt_routes_ess_build) */
     uint32_t* ess_w;
-    double* ess_r; /* ... and, for the envelope, their reliabilities (srt_envelope_ess_rel) */
-    /* the in-arc CSR the route pass reads and the load is indexed by; sorted: its lists ascend */
+    double* ess_r; /* ... and, with want_ir, their reliabilities (srt_envelope_ess_rel) */
+    /* the in-arc CSR the passes read and the load is indexed by; sorted: its lists ascend */
     const int32_t *irp, *icol;
     const uint32_t* iw;
-    const double* ir; /* the arcs' reliabilities (dense: with `envelope` only) */
+    const double* ir; /* the arcs' reliabilities (dense: with want_ir only) */
     int64_t narcs;
     int sorted;
-    int envelope;     /* set before the open: the envelope pass reads this source (ir, ms_ess_rel);
-                       * a step then runs the route pass only where a route output is wanted */
     double ms_ess_rel;
-    int rows_only;    /* set before the open: the pass reads the distance rows and the CSR alone (the
-                       * split load); a step runs the route pass only where an output is wanted */
     int chunk;        /* rows a step */
-    int32_t* dout[3]; /* pred, first, hops of the last step's rows (stride n; NULL: not asked) */
+    int32_t* dout[3]; /* pred, first, hops of the last step's rows (stride n; NULL: not kept) */
     int cnt;          /* ... how many, and their sources (NULL: the vertices from the step's r0) */
     const int32_t* srcs;
     srt_route_stats stats; /* ms_tables, ms_routes, ess_arcs, max_hops, stage_forms so far */
+
+    /* the last step's distance rows and their stride, as the passes take them (with dense as
+     * by_src: the dense table holds a row per vertex) */
+    size_t ldd() const { return (size_t)(dense ? ld : n); }
 };
 
 static int route_source_open(route_source* s, const srt_canon* c, const srt_build_opts* opts,
                              int algo, int nsub, const int32_t* verts) {
     const int n = c->n;
     const int dev = opts ? opts->device : 0;
-    srt_build_stats bs;
-    memset(&bs, 0, sizeof(bs));
+    srt_build_stats bs = {};
     s->n = n;
     s->nsub = nsub;
     s->dense = algo == SRT_ALGO_DENSE_FW;
@@ -2270,7 +2282,7 @@ static int route_source_open(route_source* s, const srt_canon* c, const srt_buil
         s->icol = s->ess_col;
         s->iw = s->ess_w;
         s->narcs = s->stats.ess_arcs;
-        if (s->envelope) {
+        if (s->want_ir) {
             TRY(srt_envelope_ess_rel(n, s->ld, s->narcs, s->ess_rp, s->ess_col, s->dr, s->st,
                                      &s->ess_r, &s->ms_ess_rel));
             s->ir = s->ess_r;
@@ -2292,11 +2304,10 @@ out:
 }
 
 /* the chunk: what is free now beyond `reserved` bytes, over a row's bytes -- the distance and
- * reliability rows of a sparse build, the outputs asked for (want) and the caller's row_extra */
-static int route_source_chunks(route_source* s, size_t reserved, size_t row_extra,
-                               const bool want[3]) {
+ * reliability rows of a sparse build, the route outputs kept (want) and the caller's row_extra */
+static int route_source_chunks(route_source* s, size_t reserved, size_t row_extra) {
     const size_t n = (size_t)s->n;
-    const int nout = (want[0] ? 1 : 0) + (want[1] ? 1 : 0) + (want[2] ? 1 : 0);
+    const int nout = (s->want[0] ? 1 : 0) + (s->want[1] ? 1 : 0) + (s->want[2] ? 1 : 0);
     int rc = SRT_OK;
     s->chunk = chunk_rows(reserved, 1, n * ((s->dense ? 0 : 12) + 4 * (size_t)nout) + row_extra,
                           s->nsub);
@@ -2306,27 +2317,25 @@ static int route_source_chunks(route_source* s, size_t reserved, size_t row_extr
         TRY(dalloc(&s->B, (void**)&s->drel, (size_t)s->chunk * n * sizeof(double)));
     }
     for (int i = 0; i < 3; i++)
-        if (want[i]) TRY(dalloc(&s->B, (void**)&s->dout[i], (size_t)s->chunk * n * sizeof(int32_t)));
+        if (s->want[i]) TRY(dalloc(&s->B, (void**)&s->dout[i], (size_t)s->chunk * n * sizeof(int32_t)));
 out:
     return rc;
 }
 
 /* the rows of the sources at slots [r0, r0 + chunk) (fewer at the end) into dout */
 static int route_source_step(route_source* s, int r0) {
-    const int n = s->n;
     int rc = SRT_OK;
     s->cnt = r0 + s->chunk < s->nsub ? s->chunk : s->nsub - r0;
     s->srcs = s->dverts ? s->dverts + r0 : NULL;
     if (!s->dense) { /* the dense table holds every row already */
-        srt_build_stats bs;
-        memset(&bs, 0, sizeof(bs));
+        srt_build_stats bs = {};
         TRY(sparse_chunk(s->sg, s->dverts, r0, s->cnt, s->dlat, s->drel, NULL, s->st, &bs));
         s->stats.ms_tables += bs.ms_total;
     }
-    if (!(s->envelope || s->rows_only) || s->dout[0] || s->dout[1] || s->dout[2])
-        TRY(srt_routes_rows_timed(n, s->cnt, s->srcs, r0, s->dense, s->dlat,
-                                  (size_t)(s->dense ? s->ld : n), s->irp, s->icol, s->iw, s->dout[0],
-                                  s->dout[1], s->dout[2], (size_t)n, s->st, &s->stats));
+    if (s->routes)
+        TRY(srt_routes_rows_timed(s->n, s->cnt, s->srcs, r0, s->dense, s->dlat, s->ldd(), s->irp,
+                                  s->icol, s->iw, s->dout[0], s->dout[1], s->dout[2], (size_t)s->n,
+                                  s->st, &s->stats));
 out:
     return rc;
 }
@@ -2342,32 +2351,8 @@ static void route_source_close(route_source* s) {
     dfree(&s->B);
 }
 
-/* one GPU: the route source's rows into the host outputs */
-static int routes_one(const srt_canon* c, const srt_build_opts* opts, int algo, int nsub,
-                      const int32_t* verts, int32_t* const hout[3], srt_route_stats* stats) {
-    const size_t w4 = (size_t)c->n * sizeof(int32_t);
-    const bool want[3] = {hout[0] != NULL, hout[1] != NULL, hout[2] != NULL};
-    route_source src = {};
-    int rc = SRT_OK;
-    TRY(route_source_open(&src, c, opts, algo, nsub, verts));
-    /* with no output asked, a row still counts as one */
-    TRY(route_source_chunks(&src, 0, want[0] || want[1] || want[2] ? 0 : w4, want));
-    for (int r0 = 0; r0 < nsub; r0 += src.chunk) {
-        TRY(route_source_step(&src, r0));
-        for (int i = 0; i < 3; i++)
-            if (hout[i])
-                TRY(table_download(hout[i] + (size_t)r0 * c->n, w4, src.dout[i], w4, w4, src.cnt,
-                                   src.st, 1));
-    }
-    if (stats) *stats = src.stats;
-out:
-    route_source_close(&src);
-    return rc;
-}
-
-/* direct mode (topology.c:1816-1858): every pair is its own edge */
-static int routes_direct(const srt_edges* g, int32_t nsrc, const int32_t* srcs,
-                         int32_t* const hout[3]) {
+/* direct mode (topology.c:1816-1858): every pair must be its own edge */
+static int direct_complete(const srt_edges* g) {
     const int64_t n = g->n;
     if (check_dense_n(g->n)) return SRT_E_RANGE;
     std::vector<uint8_t> have((size_t)((n * n + 7) / 8), 0);
@@ -2392,6 +2377,85 @@ static int routes_direct(const srt_edges* g, int32_t nsrc, const int32_t* srcs,
         srt_set_error("use_shortest_path=false requires a complete graph");
         return SRT_E_INVALID;
     }
+    return SRT_OK;
+}
+
+/* The entry of the four srt_build_* post passes, in the order that decides which error wins: the
+ * null-argument check (args), the row-chunk reset, check(&nsub) -- the sources or the demand --,
+ * then in direct mode the completeness check and direct(), else the device check and
+ * run(c, algo) on the canonical graph, whose rows must fit u32 (`pass` names their reader). A
+ * call with no source at all (an empty demand) is done once it is checked. stats (NULL: none):
+ * the caller's, zeroed in direct mode, where no pass runs. */
+template <class Check, class Direct, class Run>
+static int post_entry(const char* who, const char* pass, const srt_edges* g,
+                      const srt_build_opts* opts, bool args, void* stats, size_t stats_bytes,
+                      Check check, Direct direct, Run run) {
+    if (!args) {
+        srt_set_error("%s: null argument", who);
+        return SRT_E_ARG;
+    }
+    last_row_chunks.store(0, std::memory_order_relaxed);
+    int nsub = 0;
+    int rc = check(&nsub);
+    if (rc) return rc;
+    if (!(opts ? opts->use_shortest_path : 1)) {
+        if (stats) memset(stats, 0, stats_bytes);
+        rc = direct_complete(g);
+        return rc ? rc : direct();
+    }
+    if (nsub == 0) return SRT_OK; /* no demand: nothing to route */
+    if (srt_device_count() < 1) {
+        srt_set_error("%s: no HIP device", who);
+        return SRT_E_DEVICE;
+    }
+    return with_canon(g, opts, 1, [&](const srt_canon* c, int algo, double) {
+        if (c->wide) {
+            srt_set_error("%s: shortest-path latencies may pass the u32 range (bound %llu quanta of "
+                          "%llu ns); the %s reads u32 rows only", who,
+                          (unsigned long long)c->dist_bound, (unsigned long long)c->quantum_ns, pass);
+            return (int)SRT_E_RANGE;
+        }
+        return run(c, algo);
+    });
+}
+
+/* the source check of the passes that take a list of sources */
+static int post_check_sources(const char* who, int n, int32_t nsrc, const int32_t* srcs, int* nsub) {
+    if (check_verts(n, nsrc, srcs)) {
+        srt_set_error("%s: the sources must be 1..n strictly increasing vertex indices (or NULL "
+                      "with nsrc = n)", who);
+        return SRT_E_ARG;
+    }
+    *nsub = nsrc;
+    return SRT_OK;
+}
+
+/* one GPU: the route source's rows into the host outputs */
+static int routes_one(const srt_canon* c, const srt_build_opts* opts, int algo, int nsub,
+                      const int32_t* verts, int32_t* const hout[3], srt_route_stats* stats) {
+    const size_t w4 = (size_t)c->n * sizeof(int32_t);
+    route_source src = {};
+    int rc = SRT_OK;
+    src.routes = true;
+    for (int i = 0; i < 3; i++) src.want[i] = hout[i] != NULL;
+    TRY(route_source_open(&src, c, opts, algo, nsub, verts));
+    /* with no output asked, a row still counts as one */
+    TRY(route_source_chunks(&src, 0, hout[0] || hout[1] || hout[2] ? 0 : w4));
+    for (int r0 = 0; r0 < nsub; r0 += src.chunk) {
+        TRY(route_source_step(&src, r0));
+        for (int i = 0; i < 3; i++)
+            if (hout[i])
+                TRY(table_download(hout[i] + (size_t)r0 * c->n, w4, src.dout[i], w4, w4, src.cnt,
+                                   src.st, 1));
+    }
+    if (stats) *stats = src.stats;
+out:
+    route_source_close(&src);
+    return rc;
+}
+
+/* direct mode: every pair is its own edge */
+static int routes_direct(int32_t n, int32_t nsrc, const int32_t* srcs, int32_t* const hout[3]) {
     for (int32_t i = 0; i < nsrc; i++) {
         const int32_t s = srcs ? srcs[i] : i;
         for (int32_t t = 0; t < n; t++) {
@@ -2407,59 +2471,29 @@ static int routes_direct(const srt_edges* g, int32_t nsrc, const int32_t* srcs,
 extern "C" int srt_build_routes(const srt_edges* g, const srt_build_opts* opts, int32_t nsrc,
                                 const int32_t* srcs, int32_t* pred, int32_t* first_hop,
                                 int32_t* hops, srt_route_stats* stats) {
-    if (!g || g->n <= 0) {
-        srt_set_error("srt_build_routes: null argument");
-        return SRT_E_ARG;
-    }
-    if (check_verts(g->n, nsrc, srcs)) {
-        srt_set_error("srt_build_routes: the sources must be 1..n strictly increasing vertex "
-                      "indices (or NULL with nsrc = n)");
-        return SRT_E_ARG;
-    }
-    last_row_chunks.store(0, std::memory_order_relaxed);
+    const char* who = "srt_build_routes";
     int32_t* const hout[3] = {pred, first_hop, hops};
-    const int use_sp = opts ? opts->use_shortest_path : 1;
-    if (!use_sp) {
-        if (stats) memset(stats, 0, sizeof(*stats));
-        return routes_direct(g, nsrc, srcs, hout);
-    }
-    if (srt_device_count() < 1) {
-        srt_set_error("srt_build_routes: no HIP device");
-        return SRT_E_DEVICE;
-    }
-    return with_canon(g, opts, 1, [&](const srt_canon* c, int algo, double) {
-        if (c->wide) {
-            srt_set_error("srt_build_routes: shortest-path latencies may pass the u32 range (bound "
-                          "%llu quanta of %llu ns); the route pass reads u32 rows only",
-                          (unsigned long long)c->dist_bound, (unsigned long long)c->quantum_ns);
-            return (int)SRT_E_RANGE;
-        }
-        return routes_one(c, opts, algo, nsrc, srcs, hout, stats);
-    });
+    return post_entry(
+        who, "route pass", g, opts, g && g->n > 0, stats, sizeof(*stats),
+        [&](int* nsub) { return post_check_sources(who, g->n, nsrc, srcs, nsub); },
+        [&] { return routes_direct(g->n, nsrc, srcs, hout); },
+        [&](const srt_canon* c, int algo) { return routes_one(c, opts, algo, nsrc, srcs, hout, stats); });
 }
 
 /* ------------------------------------------------------------------------------------------ */
 /* Reliability envelope (envelope.hip): the distance rows of the route source, then the bounds  */
-/* over every tie order; no route output is wanted, so its steps skip the route pass.           */
+/* over every tie order; it needs no route pass, so its steps run none.                         */
 /* ------------------------------------------------------------------------------------------ */
 extern "C" int srt_envelope_rows_device(const srt_sparse_graph* g, int32_t nsrc, const int32_t* srcs,
                                         int32_t src_begin, const uint32_t* lat_rows, size_t ldl,
                                         double* rel_lo, double* rel_hi, size_t ldo, void* stream,
                                         srt_envelope_stats* stats) {
-    if (!g || nsrc < 1 || !lat_rows || ldl < (size_t)g->n ||
-        (!srcs && (src_begin < 0 || (int64_t)src_begin + nsrc > g->n))) {
-        srt_set_error("srt_envelope_rows_device: bad arguments");
-        return SRT_E_ARG;
-    }
-    if (g->wide) {
-        srt_set_error("srt_envelope_rows_device: shortest-path latencies may pass the u32 range; the "
-                      "envelope pass reads u32 rows only");
-        return SRT_E_RANGE;
-    }
-    srt_envelope_stats local;
-    memset(&local, 0, sizeof(local));
-    const int rc = srt_envelope_rows(g->n, nsrc, srcs, src_begin, 0, lat_rows, ldl, g->irp, g->icol,
-                                     g->iw, g->ir, rel_lo, rel_hi, ldo, (hipStream_t)stream, &local);
+    int rc = rows_device_check("srt_envelope_rows_device", "envelope pass", g, nsrc, srcs, src_begin,
+                               lat_rows, ldl);
+    if (rc) return rc;
+    srt_envelope_stats local = {};
+    rc = srt_envelope_rows(g->n, nsrc, srcs, src_begin, 0, lat_rows, ldl, g->irp, g->icol, g->iw,
+                           g->ir, rel_lo, rel_hi, ldo, (hipStream_t)stream, &local);
     if (!rc && stats) *stats = local;
     return rc;
 }
@@ -2468,22 +2502,19 @@ extern "C" int srt_envelope_rows_device(const srt_sparse_graph* g, int32_t nsrc,
 static int envelope_one(const srt_canon* c, const srt_build_opts* opts, int algo, int nsub,
                         const int32_t* verts, double* hlo, double* hhi, srt_envelope_stats* stats) {
     const size_t n = (size_t)c->n, w8 = n * sizeof(double);
-    const bool none[3] = {false, false, false};
     route_source src = {};
-    srt_envelope_stats es;
+    srt_envelope_stats es = {};
     double *dlo = NULL, *dhi = NULL;
     int rc = SRT_OK;
-    memset(&es, 0, sizeof(es));
-    src.envelope = 1;
+    src.want_ir = true;
     TRY(route_source_open(&src, c, opts, algo, nsub, verts));
-    TRY(route_source_chunks(&src, 0, 2 * w8, none)); /* 16 B per pair: lo and hi */
+    TRY(route_source_chunks(&src, 0, 2 * w8)); /* 16 B per pair: lo and hi */
     TRY(dalloc(&src.B, (void**)&dlo, (size_t)src.chunk * w8));
     TRY(dalloc(&src.B, (void**)&dhi, (size_t)src.chunk * w8));
     for (int r0 = 0; r0 < nsub; r0 += src.chunk) {
         TRY(route_source_step(&src, r0));
-        TRY(srt_envelope_rows(c->n, src.cnt, src.srcs, r0, src.dense, src.dlat,
-                              src.dense ? (size_t)src.ld : n, src.irp, src.icol, src.iw, src.ir, dlo,
-                              dhi, n, src.st, &es));
+        TRY(srt_envelope_rows(c->n, src.cnt, src.srcs, r0, src.dense, src.dlat, src.ldd(), src.irp,
+                              src.icol, src.iw, src.ir, dlo, dhi, n, src.st, &es));
         if (hlo) TRY(table_download(hlo + (size_t)r0 * n, w8, dlo, w8, w8, src.cnt, src.st, 1));
         if (hhi) TRY(table_download(hhi + (size_t)r0 * n, w8, dhi, w8, w8, src.cnt, src.st, 1));
     }
@@ -2533,41 +2564,22 @@ static int envelope_direct(const srt_edges* g, int32_t nsrc, const int32_t* srcs
 extern "C" int srt_build_rel_envelope(const srt_edges* g, const srt_build_opts* opts, int32_t nsrc,
                                       const int32_t* srcs, double* rel_lo, double* rel_hi,
                                       srt_envelope_stats* stats) {
-    if (!g || g->n <= 0) {
-        srt_set_error("srt_build_rel_envelope: null argument");
-        return SRT_E_ARG;
-    }
-    if (check_verts(g->n, nsrc, srcs)) {
-        srt_set_error("srt_build_rel_envelope: the sources must be 1..n strictly increasing vertex "
-                      "indices (or NULL with nsrc = n)");
-        return SRT_E_ARG;
-    }
-    last_row_chunks.store(0, std::memory_order_relaxed);
-    const int use_sp = opts ? opts->use_shortest_path : 1;
-    if (!use_sp) {
-        int32_t* const none[3] = {NULL, NULL, NULL};
-        if (stats) memset(stats, 0, sizeof(*stats));
-        const int rc = routes_direct(g, 0, NULL, none); /* the completeness check and its error */
-        return rc ? rc : envelope_direct(g, nsrc, srcs, rel_lo, rel_hi);
-    }
-    if (srt_device_count() < 1) {
-        srt_set_error("srt_build_rel_envelope: no HIP device");
-        return SRT_E_DEVICE;
-    }
-    return with_canon(g, opts, 1, [&](const srt_canon* c, int algo, double) {
-        if (c->wide) {
-            srt_set_error("srt_build_rel_envelope: shortest-path latencies may pass the u32 range "
-                          "(bound %llu quanta of %llu ns); the envelope pass reads u32 rows only",
-                          (unsigned long long)c->dist_bound, (unsigned long long)c->quantum_ns);
-            return (int)SRT_E_RANGE;
-        }
-        return envelope_one(c, opts, algo, nsrc, srcs, rel_lo, rel_hi, stats);
-    });
+    const char* who = "srt_build_rel_envelope";
+    return post_entry(
+        who, "envelope pass", g, opts, g && g->n > 0, stats, sizeof(*stats),
+        [&](int* nsub) { return post_check_sources(who, g->n, nsrc, srcs, nsub); },
+        [&] { return envelope_direct(g, nsrc, srcs, rel_lo, rel_hi); },
+        [&](const srt_canon* c, int algo) {
+            return envelope_one(c, opts, algo, nsrc, srcs, rel_lo, rel_hi, stats);
+        });
 }
 
 /* ------------------------------------------------------------------------------------------ */
-/* Link load (linkload.hip): the route pass over each chunk of rows, then the load pass over    */
-/* the pred and hops rows it wrote and the chunk's demand rows, which are built on the device.  */
+/* The two loads over a demand: the link load (linkload.hip: the route pass over each chunk of  */
+/* rows, then the load pass over the pred and hops rows it wrote) and the split load            */
+/* (splitload.hip: every tie split evenly, over the distance rows alone, so its steps run no    */
+/* route pass). Both read the chunk's demand rows, which are built on the device, and differ in */
+/* the load word T -- u64 or f64 -- and in the pass they call.                                  */
 /* ------------------------------------------------------------------------------------------ */
 extern "C" int srt_sparse_graph_in_arcs(const srt_sparse_graph* g, const int32_t** rowptr,
                                         const int32_t** tails) {
@@ -2590,12 +2602,71 @@ extern "C" int srt_link_load_rows_device(const srt_sparse_graph* g, int32_t nsrc
         srt_set_error("srt_link_load_rows_device: bad arguments");
         return SRT_E_ARG;
     }
-    srt_link_load_stats local;
-    memset(&local, 0, sizeof(local));
+    srt_link_load_stats local = {};
     const int rc = srt_link_load_rows(g->n, nsrc, srcs, src_begin, pred, hops, ldp, dem, ldd, g->irp,
                                       g->icol, load, through, 1, totals, (hipStream_t)stream,
                                       &local.max_hops, &local.forms, &local.ms_load);
     if (!rc && stats) *stats = local;
+    return rc;
+}
+
+extern "C" int srt_split_load_rows_device(const srt_sparse_graph* g, int32_t nsrc,
+                                          const int32_t* srcs, int32_t src_begin,
+                                          const uint32_t* lat_rows, size_t ldl, const uint64_t* dem,
+                                          size_t ldd, double* load, double* through,
+                                          uint64_t* totals, void* stream,
+                                          srt_split_load_stats* stats) {
+    int rc = rows_device_check("srt_split_load_rows_device", "split-load pass", g, nsrc, srcs,
+                               src_begin, lat_rows, ldl);
+    if (rc) return rc;
+    srt_split_load_stats local = {};
+    rc = srt_split_load_rows(g->n, nsrc, srcs, src_begin, 0, lat_rows, ldl, dem, ldd, g->irp, g->icol,
+                             g->iw, load, through, totals, (hipStream_t)stream, &local);
+    if (!rc && stats) *stats = local;
+    return rc;
+}
+
+/* A load over rows [row0, row0 + nrows) of a finished dense build on the device: the essential
+ * in-arc CSR into rowptr / tails (*narcs of them, set even where arc_cap refuses them), load,
+ * through and totals zeroed, then pass(irp, icol, iw). args: the caller's own argument checks. */
+template <class T, class Pass>
+static int load_dense_device(const char* who, bool args, int32_t n, int32_t ld, int32_t directed,
+                             const uint32_t* w, const uint32_t* lat, int32_t row0, int32_t nrows,
+                             int64_t arc_cap, int32_t* rowptr, int32_t* tails, T* load,
+                             int64_t* narcs, T* through, uint64_t* totals, hipStream_t st,
+                             Pass pass) {
+    if (!args || n < 1 || ld < n || !w || !lat || row0 < 0 || nrows < 1 ||
+        (int64_t)row0 + nrows > n || arc_cap < 0 || !rowptr || !tails || !load || !through ||
+        !totals) {
+        srt_set_error("%s: bad arguments (n = %d, ld = %d, rows [%d, %d))", who, n, ld, row0,
+                      row0 + nrows);
+        return SRT_E_ARG;
+    }
+    if (n > SRT_DENSE_MAX_N) {
+        srt_set_error("%s: n = %d beyond the dense limit %d", who, n, SRT_DENSE_MAX_N);
+        return SRT_E_RANGE;
+    }
+    int32_t *irp = NULL, *icol = NULL;
+    uint32_t* iw = NULL;
+    int64_t arcs = 0;
+    double ms_ess = 0;
+    int rc = srt_routes_ess_build(n, ld, directed, w, lat, st, &irp, &icol, &iw, &arcs, &ms_ess);
+    if (!rc && narcs) *narcs = arcs;
+    if (!rc && arcs > arc_cap) {
+        srt_set_error("%s: %lld essential arcs, room for %lld", who, (long long)arcs,
+                      (long long)arc_cap);
+        rc = SRT_E_RANGE;
+    }
+    if (!rc) {
+        TRYHIP(hipMemcpyAsync(rowptr, irp, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        TRYHIP(hipMemcpyAsync(tails, icol, (size_t)arcs * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        TRYHIP(hipMemsetAsync(load, 0, (size_t)arcs * sizeof(T), st));
+        TRYHIP(hipMemsetAsync(through, 0, (size_t)n * sizeof(T), st));
+        TRYHIP(hipMemsetAsync(totals, 0, 3 * sizeof(uint64_t), st));
+        rc = pass(irp, icol, iw);
+    }
+out:
+    srt_routes_ess_free(irp, icol, iw, st);
     return rc;
 }
 
@@ -2606,72 +2677,91 @@ extern "C" int srt_link_load_dense_device(int32_t n, int32_t ld, int32_t directe
                                           int32_t* rowptr, int32_t* tails, uint64_t* load,
                                           int64_t* narcs, uint64_t* through, uint64_t* totals,
                                           void* stream, srt_link_load_stats* stats) {
-    if (n < 1 || ld < n || !w || !lat || row0 < 0 || nrows < 1 || (int64_t)row0 + nrows > n ||
-        arc_cap < 0 || !rowptr || !tails || !load || !through || !totals) {
-        srt_set_error("srt_link_load_dense_device: bad arguments (n = %d, ld = %d, rows [%d, %d))", n,
-                      ld, row0, row0 + nrows);
-        return SRT_E_ARG;
-    }
-    if (n > SRT_DENSE_MAX_N) {
-        srt_set_error("srt_link_load_dense_device: n = %d beyond the dense limit %d", n,
-                      SRT_DENSE_MAX_N);
-        return SRT_E_RANGE;
-    }
     hipStream_t st = (hipStream_t)stream;
-    srt_link_load_stats local;
-    memset(&local, 0, sizeof(local));
-    int32_t *irp = NULL, *icol = NULL;
-    uint32_t* iw = NULL;
-    int64_t arcs = 0;
-    double ms_ess = 0;
-    int rc = srt_routes_ess_build(n, ld, directed, w, lat, st, &irp, &icol, &iw, &arcs, &ms_ess);
-    if (!rc && narcs) *narcs = arcs;
-    if (!rc && arcs > arc_cap) {
-        srt_set_error("srt_link_load_dense_device: %lld essential arcs, room for %lld",
-                      (long long)arcs, (long long)arc_cap);
-        rc = SRT_E_RANGE;
-    }
-    if (!rc) {
-        TRYHIP(hipMemcpyAsync(rowptr, irp, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-        TRYHIP(hipMemcpyAsync(tails, icol, (size_t)arcs * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-        TRYHIP(hipMemsetAsync(load, 0, (size_t)arcs * sizeof(uint64_t), st));
-        TRYHIP(hipMemsetAsync(through, 0, (size_t)n * sizeof(uint64_t), st));
-        TRYHIP(hipMemsetAsync(totals, 0, 3 * sizeof(uint64_t), st));
-        /* an undirected graph's essential lists are compacted in column order, a directed one's
-         * through per-head cursors in no order */
-        rc = srt_link_load_rows(n, nrows, NULL, row0, pred, hops, ldp, dem, ldd, irp, icol, load,
-                                through, directed ? 0 : 1, totals, st, &local.max_hops,
-                                &local.forms, &local.ms_load);
-    }
-out:
-    srt_routes_ess_free(irp, icol, iw, st);
+    srt_link_load_stats local = {};
+    const int rc = load_dense_device(
+        "srt_link_load_dense_device", true, n, ld, directed, w, lat, row0, nrows, arc_cap, rowptr,
+        tails, load, narcs, through, totals, st,
+        [&](const int32_t* irp, const int32_t* icol, const uint32_t*) {
+            /* an undirected graph's essential lists are compacted in column order, a directed
+             * one's through per-head cursors in no order */
+            return srt_link_load_rows(n, nrows, NULL, row0, pred, hops, ldp, dem, ldd, irp, icol,
+                                      load, through, directed ? 0 : 1, totals, st, &local.max_hops,
+                                      &local.forms, &local.ms_load);
+        });
     if (!rc && stats) *stats = local;
     return rc;
 }
 
-extern "C" void srt_link_load_free(srt_link_load* ll) {
-    if (!ll) return;
-    free(ll->tail);
-    free(ll->head);
-    free(ll->load);
-    free(ll->through);
-    free(ll);
+extern "C" int srt_split_load_dense_device(int32_t n, int32_t ld, int32_t directed,
+                                           const uint32_t* w, const uint32_t* lat, int32_t row0,
+                                           int32_t nrows, const uint64_t* dem, size_t ldd,
+                                           int64_t arc_cap, int32_t* rowptr, int32_t* tails,
+                                           double* load, int64_t* narcs, double* through,
+                                           uint64_t* totals, void* stream,
+                                           srt_split_load_stats* stats) {
+    hipStream_t st = (hipStream_t)stream;
+    srt_split_load_stats local = {};
+    const int rc = load_dense_device(
+        "srt_split_load_dense_device", dem != NULL, n, ld, directed, w, lat, row0, nrows, arc_cap,
+        rowptr, tails, load, narcs, through, totals, st,
+        [&](const int32_t* irp, const int32_t* icol, const uint32_t* iw) {
+            return srt_split_load_rows(n, nrows, NULL, row0, 0, lat + (size_t)row0 * ld, (size_t)ld,
+                                       dem, ldd, irp, icol, iw, load, through, totals, st, &local);
+        });
+    if (!rc && stats) *stats = local;
+    return rc;
 }
 
-/* an all-zero result over n vertices with room for narcs arcs */
-static srt_link_load* link_load_new(int64_t n, int64_t narcs) {
-    srt_link_load* ll = (srt_link_load*)calloc(1, sizeof(srt_link_load));
-    if (!ll) return NULL;
-    const size_t na = (size_t)(narcs > 0 ? narcs : 1);
-    ll->tail = (int32_t*)malloc(na * sizeof(int32_t));
-    ll->head = (int32_t*)malloc(na * sizeof(int32_t));
-    ll->load = (uint64_t*)malloc(na * sizeof(uint64_t));
-    ll->through = (uint64_t*)calloc((size_t)(n > 0 ? n : 1), sizeof(uint64_t));
-    if (!ll->tail || !ll->head || !ll->load || !ll->through) {
-        srt_link_load_free(ll);
+template <class R>
+static void load_free(R* res) {
+    if (!res) return;
+    free(res->tail);
+    free(res->head);
+    free(res->load);
+    free(res->through);
+    free(res);
+}
+
+extern "C" void srt_link_load_free(srt_link_load* ll) { load_free(ll); }
+extern "C" void srt_split_load_free(srt_split_load* sl) { load_free(sl); }
+
+/* k arcs (which may be 0: room for one stays, so no array is NULL) as the result's, by
+ * (tail, head): copied from tail, head and load, or (tail NULL) left for the caller to fill */
+template <class T, class R>
+static int set_arcs(const char* who, R* res, size_t k, const int32_t* tail = NULL,
+                    const int32_t* head = NULL, const T* load = NULL) {
+    const size_t room = k ? k : 1;
+    free(res->tail);
+    free(res->head);
+    free(res->load);
+    res->tail = (int32_t*)malloc(room * sizeof(int32_t));
+    res->head = (int32_t*)malloc(room * sizeof(int32_t));
+    res->load = (T*)malloc(room * sizeof(T));
+    if (!res->tail || !res->head || !res->load) {
+        srt_set_error("%s: out of memory for %zu arcs", who, k);
+        return SRT_E_NOMEM;
+    }
+    if (k && tail) {
+        memcpy(res->tail, tail, k * sizeof(int32_t));
+        memcpy(res->head, head, k * sizeof(int32_t));
+        memcpy(res->load, load, k * sizeof(T));
+    }
+    res->narcs = (int64_t)k;
+    return SRT_OK;
+}
+
+/* an all-zero result over n vertices with no arc */
+template <class T, class R>
+static R* load_new(const char* who, int n) {
+    R* res = (R*)calloc(1, sizeof(R));
+    if (res) res->through = (T*)calloc((size_t)n, sizeof(T));
+    if (!res || !res->through || set_arcs<T>(who, res, 0)) {
+        load_free(res);
+        srt_set_error("%s: out of memory", who);
         return NULL;
     }
-    return ll;
+    return res;
 }
 
 /* the demand of a call: uniform over the sources verts (NULL: every vertex), or COO entries whose
@@ -2693,15 +2783,9 @@ static int ll_demand_parse(const char* who, int n, int32_t nsrc, const int32_t* 
                            uint64_t* total) {
     *total = 0;
     if (ndem < 0) {
-        if (check_verts(n, nsrc, srcs)) {
-            srt_set_error("%s: the sources must be 1..n strictly increasing vertex "
-                          "indices (or NULL with nsrc = n)", who);
-            return SRT_E_ARG;
-        }
-        dm->nsub = nsrc;
         dm->verts = srcs;
         *total = (uint64_t)nsrc * (uint64_t)n;
-        return SRT_OK;
+        return post_check_sources(who, n, nsrc, srcs, &dm->nsub);
     }
     if (srcs || (ndem > 0 && (!dsrc || !dtgt || !dval))) {
         srt_set_error("%s: COO demands take their sources from dsrc (srcs must "
@@ -2734,422 +2818,40 @@ static int ll_demand_parse(const char* who, int n, int32_t nsrc, const int32_t* 
     return SRT_OK;
 }
 
-/* the positions of a by-head CSR that carry load, as (tail, head, load) sorted by (tail, head) */
-static int link_load_collect(int n, const int32_t* irp, const int32_t* icol, const uint64_t* load,
-                             srt_link_load* ll) {
-    const int64_t na = irp[n];
-    std::vector<int64_t> start((size_t)n + 1, 0);
-    int64_t cnt = 0;
-    for (int64_t k = 0; k < na; k++)
-        if (load[k]) {
-            start[(size_t)icol[k] + 1]++;
-            cnt++;
-        }
-    for (int v = 0; v < n; v++) start[(size_t)v + 1] += start[v];
-    const size_t room = (size_t)(cnt > 0 ? cnt : 1);
-    int32_t* tail = (int32_t*)malloc(room * sizeof(int32_t));
-    int32_t* head = (int32_t*)malloc(room * sizeof(int32_t));
-    uint64_t* ld = (uint64_t*)malloc(room * sizeof(uint64_t));
-    if (!tail || !head || !ld) {
-        free(tail);
-        free(head);
-        free(ld);
-        srt_set_error("srt_build_link_load: out of memory for %lld arcs", (long long)cnt);
-        return SRT_E_NOMEM;
-    }
-    /* heads ascend in the outer loop, so each tail's arcs come out by head */
-    for (int t = 0; t < n; t++)
-        for (int64_t k = irp[t]; k < irp[t + 1]; k++)
-            if (load[k]) {
-                const int64_t o = start[icol[k]]++;
-                tail[o] = icol[k];
-                head[o] = t;
-                ld[o] = load[k];
-            }
-    free(ll->tail);
-    free(ll->head);
-    free(ll->load);
-    ll->tail = tail;
-    ll->head = head;
-    ll->load = ld;
-    ll->narcs = cnt;
-    return SRT_OK;
-}
-
-/* one GPU: the load pass behind the route pass of every chunk of the route source, over the
- * chunk's demand rows, which are built on the device */
-static int link_load_one(const srt_canon* c, const srt_build_opts* opts, int algo,
-                         const ll_demand* dm, srt_link_load* ll) {
-    const int n = c->n;
-    const int nsub = dm->nsub;
-    route_source src = {};
-    dbufs B;
-    B.k = 0;
+/* The demand rows of a load's chunks on the device: open sizes them (in B) for chunks of `chunk`
+ * of the demand's rows, step builds the u64 rows ddem (stride n) of the cnt rows from r0 on st. */
+struct demand_feed {
+    const ll_demand* dm;
+    int n;
+    uint64_t* ddem = NULL;
+    int64_t* drowptr = NULL; /* COO: the chunk's row offsets, its targets and its values */
     int32_t* dtgt = NULL;
-    int64_t* drowptr = NULL;
-    uint64_t *ddem = NULL, *dval = NULL, *dload = NULL, *dthrough = NULL, *dtot = NULL;
-    int64_t narcs = 0, max_ent = 0;
-    int32_t forms = 0, mh = 0;
-    uint64_t htot[3] = {0, 0, 0};
-    const bool want[3] = {true, false, true}; /* pred and hops */
-    hipStream_t st = NULL;
-    std::vector<int32_t> hirp, hicol;
-    std::vector<uint64_t> hload;
+    uint64_t* dval = NULL;
     std::vector<int64_t> rel_rowptr;
-    int rc = SRT_OK;
-    TRY(route_source_open(&src, c, opts, algo, nsub, dm->verts));
-    st = src.st;
-    narcs = src.narcs;
-    /* beside the source's rows: the load itself, and a u64 demand row per source row */
-    TRY(route_source_chunks(&src, (size_t)narcs * 8, (size_t)n * 8, want));
-    TRY(dalloc(&B, (void**)&ddem, (size_t)src.chunk * n * sizeof(uint64_t)));
-    TRY(dalloc(&B, (void**)&dload, (size_t)narcs * sizeof(uint64_t)));
-    TRY(dalloc(&B, (void**)&dthrough, (size_t)n * sizeof(uint64_t)));
-    TRY(dalloc(&B, (void**)&dtot, 3 * sizeof(uint64_t)));
-    TRYHIP(hipMemsetAsync(dload, 0, (size_t)narcs * sizeof(uint64_t), st));
-    TRYHIP(hipMemsetAsync(dthrough, 0, (size_t)n * sizeof(uint64_t), st));
-    TRYHIP(hipMemsetAsync(dtot, 0, 3 * sizeof(uint64_t), st));
-    if (dm->rowptr) { /* room for the COO entries of the largest chunk */
-        for (int r0 = 0; r0 < nsub; r0 += src.chunk) {
-            const int r1 = r0 + src.chunk < nsub ? r0 + src.chunk : nsub;
-            const int64_t e = dm->rowptr[r1] - dm->rowptr[r0];
-            max_ent = e > max_ent ? e : max_ent;
-        }
-        TRY(dalloc(&B, (void**)&drowptr, ((size_t)src.chunk + 1) * sizeof(int64_t)));
-        TRY(dalloc(&B, (void**)&dtgt, (size_t)max_ent * sizeof(int32_t)));
-        TRY(dalloc(&B, (void**)&dval, (size_t)max_ent * sizeof(uint64_t)));
-        rel_rowptr.resize((size_t)src.chunk + 1);
-    }
-    for (int r0 = 0; r0 < nsub; r0 += src.chunk) {
-        TRY(route_source_step(&src, r0));
-        const int cnt = src.cnt;
-        if (dm->rowptr) { /* the chunk's entries, their row offsets re-based to its first row */
-            const int64_t e0 = dm->rowptr[r0], ne = dm->rowptr[r0 + cnt] - e0;
-            for (int i = 0; i <= cnt; i++) rel_rowptr[i] = dm->rowptr[r0 + i] - e0;
-            TRYHIP(hipMemcpyAsync(drowptr, rel_rowptr.data(), ((size_t)cnt + 1) * sizeof(int64_t),
-                                  hipMemcpyHostToDevice, st));
-            if (ne > 0) {
-                TRYHIP(hipMemcpyAsync(dtgt, dm->tgt + e0, (size_t)ne * sizeof(int32_t),
-                                      hipMemcpyHostToDevice, st));
-                TRYHIP(hipMemcpyAsync(dval, dm->val + e0, (size_t)ne * sizeof(uint64_t),
-                                      hipMemcpyHostToDevice, st));
-            }
-            TRYHIP(hipStreamSynchronize(st)); /* rel_rowptr is reused by the next chunk */
-        }
-        TRY(srt_link_load_demand_rows(n, cnt, drowptr, dtgt, dval, ddem, (size_t)n, st));
-        TRY(srt_link_load_rows(n, cnt, src.srcs, r0, src.dout[0], src.dout[2], (size_t)n, ddem,
-                               (size_t)n, src.irp, src.icol, dload, dthrough, src.sorted, dtot, st,
-                               &mh, &forms, &ll->ms_load));
-    }
-    hirp.resize((size_t)n + 1);
-    hicol.resize((size_t)(narcs > 0 ? narcs : 1));
-    hload.resize((size_t)(narcs > 0 ? narcs : 1));
-    TRYHIP(hipMemcpyAsync(hirp.data(), src.irp, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (narcs > 0) {
-        TRYHIP(hipMemcpyAsync(hicol.data(), src.icol, (size_t)narcs * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        TRYHIP(hipMemcpyAsync(hload.data(), dload, (size_t)narcs * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    }
-    TRYHIP(hipMemcpyAsync(ll->through, dthrough, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    TRYHIP(hipMemcpyAsync(htot, dtot, sizeof(htot), hipMemcpyDeviceToHost, st));
-    TRYHIP(hipStreamSynchronize(st));
-    TRY(link_load_collect(n, hirp.data(), hicol.data(), hload.data(), ll));
-    ll->routed = htot[0];
-    ll->unrouted = htot[1];
-    ll->self_demand = htot[2];
-    ll->ms_tables = src.stats.ms_tables;
-    ll->ms_routes = src.stats.ms_routes;
-    ll->max_hops = mh;
-    ll->forms = forms;
-out:
-    route_source_close(&src);
-    dfree(&B);
-    return rc;
-}
 
-/* direct mode (topology.c:1816-1858): every pair is its own edge, so load(s -> t) = c(s, t) */
-static int link_load_direct(const srt_edges* g, const ll_demand* dm, srt_link_load* ll) {
-    const int n = g->n;
-    std::vector<int32_t> tail, head;
-    std::vector<uint64_t> load, row;
-    if (dm->rowptr) row.assign((size_t)n, 0);
-    for (int32_t i = 0; i < dm->nsub; i++) {
-        const int32_t s = dm->verts ? dm->verts[i] : i;
-        if (dm->rowptr) {
-            for (int64_t k = dm->rowptr[i]; k < dm->rowptr[i + 1]; k++) row[dm->tgt[k]] += dm->val[k];
-        }
-        for (int32_t t = 0; t < n; t++) {
-            const uint64_t cst = dm->rowptr ? row[t] : 1;
-            if (dm->rowptr) row[t] = 0;
-            if (!cst) continue;
-            if (t == s) {
-                ll->self_demand += cst;
-                continue;
+    int open(dbufs* B, const ll_demand* demand, int nverts, int chunk) {
+        int rc = SRT_OK;
+        dm = demand;
+        n = nverts;
+        TRY(dalloc(B, (void**)&ddem, (size_t)chunk * n * sizeof(uint64_t)));
+        if (dm->rowptr) { /* room for the COO entries of the largest chunk */
+            int64_t max_ent = 0;
+            for (int r0 = 0; r0 < dm->nsub; r0 += chunk) {
+                const int r1 = r0 + chunk < dm->nsub ? r0 + chunk : dm->nsub;
+                const int64_t e = dm->rowptr[r1] - dm->rowptr[r0];
+                max_ent = e > max_ent ? e : max_ent;
             }
-            ll->routed += cst;
-            tail.push_back(s);
-            head.push_back(t);
-            load.push_back(cst);
+            TRY(dalloc(B, (void**)&drowptr, ((size_t)chunk + 1) * sizeof(int64_t)));
+            TRY(dalloc(B, (void**)&dtgt, (size_t)max_ent * sizeof(int32_t)));
+            TRY(dalloc(B, (void**)&dval, (size_t)max_ent * sizeof(uint64_t)));
+            rel_rowptr.resize((size_t)chunk + 1);
         }
-    }
-    const size_t k = tail.size();
-    if (k) {
-        int32_t* nt = (int32_t*)realloc(ll->tail, k * sizeof(int32_t));
-        if (nt) ll->tail = nt;
-        int32_t* nh = (int32_t*)realloc(ll->head, k * sizeof(int32_t));
-        if (nh) ll->head = nh;
-        uint64_t* nl = (uint64_t*)realloc(ll->load, k * sizeof(uint64_t));
-        if (nl) ll->load = nl;
-        if (!nt || !nh || !nl) {
-            srt_set_error("srt_build_link_load: out of memory for %zu arcs", k);
-            return SRT_E_NOMEM;
-        }
-        memcpy(ll->tail, tail.data(), k * sizeof(int32_t));
-        memcpy(ll->head, head.data(), k * sizeof(int32_t));
-        memcpy(ll->load, load.data(), k * sizeof(uint64_t));
-    }
-    ll->narcs = (int64_t)k;
-    ll->max_hops = k ? 1 : 0;
-    return SRT_OK;
-}
-
-extern "C" int srt_build_link_load(const srt_edges* g, const srt_build_opts* opts, int32_t nsrc,
-                                   const int32_t* srcs, int64_t ndem, const int32_t* dsrc,
-                                   const int32_t* dtgt, const uint64_t* dval, srt_link_load** out) {
-    if (out) *out = NULL;
-    if (!g || g->n <= 0 || !out) {
-        srt_set_error("srt_build_link_load: null argument");
-        return SRT_E_ARG;
-    }
-    last_row_chunks.store(0, std::memory_order_relaxed);
-    const int n = g->n;
-    ll_demand dm = {0, NULL, NULL, NULL, NULL};
-    std::vector<int32_t> dverts;
-    std::vector<int64_t> rowptr;
-    uint64_t total = 0;
-    const int drc = ll_demand_parse("srt_build_link_load", n, nsrc, srcs, ndem, dsrc, dtgt, dval, &dm,
-                                    &dverts, &rowptr, &total);
-    if (drc) return drc;
-    srt_link_load* ll = link_load_new(n, 0);
-    if (!ll) {
-        srt_set_error("srt_build_link_load: out of memory");
-        return SRT_E_NOMEM;
-    }
-    int rc = SRT_OK;
-    const int use_sp = opts ? opts->use_shortest_path : 1;
-    if (!use_sp) {
-        int32_t* const none[3] = {NULL, NULL, NULL};
-        rc = routes_direct(g, 0, NULL, none); /* the completeness check and its error */
-        if (!rc) rc = link_load_direct(g, &dm, ll);
-    } else if (dm.nsub == 0) {
-        rc = SRT_OK; /* no demand: nothing to route */
-    } else if (srt_device_count() < 1) {
-        srt_set_error("srt_build_link_load: no HIP device");
-        rc = SRT_E_DEVICE;
-    } else {
-        rc = with_canon(g, opts, 1, [&](const srt_canon* c, int algo, double) {
-            if (c->wide) {
-                srt_set_error("srt_build_link_load: shortest-path latencies may pass the u32 range "
-                              "(bound %llu quanta of %llu ns); the route pass reads u32 rows only",
-                              (unsigned long long)c->dist_bound, (unsigned long long)c->quantum_ns);
-                return (int)SRT_E_RANGE;
-            }
-            ll->ms_load = 0;
-            return link_load_one(c, opts, algo, &dm, ll);
-        });
-    }
-    if (rc) {
-        srt_link_load_free(ll);
+    out:
         return rc;
     }
-    *out = ll;
-    return SRT_OK;
-}
 
-/* ------------------------------------------------------------------------------------------ */
-/* Split load (splitload.hip): the distance rows of the route source, then the load with every  */
-/* tie split evenly over the chunk's demand rows; no route output is wanted, so its steps skip  */
-/* the route pass.                                                                              */
-/* ------------------------------------------------------------------------------------------ */
-extern "C" int srt_split_load_rows_device(const srt_sparse_graph* g, int32_t nsrc,
-                                          const int32_t* srcs, int32_t src_begin,
-                                          const uint32_t* lat_rows, size_t ldl, const uint64_t* dem,
-                                          size_t ldd, double* load, double* through,
-                                          uint64_t* totals, void* stream,
-                                          srt_split_load_stats* stats) {
-    if (!g || nsrc < 1 || !lat_rows || ldl < (size_t)g->n ||
-        (!srcs && (src_begin < 0 || (int64_t)src_begin + nsrc > g->n))) {
-        srt_set_error("srt_split_load_rows_device: bad arguments");
-        return SRT_E_ARG;
-    }
-    if (g->wide) {
-        srt_set_error("srt_split_load_rows_device: shortest-path latencies may pass the u32 range; "
-                      "the split-load pass reads u32 rows only");
-        return SRT_E_RANGE;
-    }
-    srt_split_load_stats local;
-    memset(&local, 0, sizeof(local));
-    const int rc = srt_split_load_rows(g->n, nsrc, srcs, src_begin, 0, lat_rows, ldl, dem, ldd,
-                                       g->irp, g->icol, g->iw, load, through, totals,
-                                       (hipStream_t)stream, &local);
-    if (!rc && stats) *stats = local;
-    return rc;
-}
-
-extern "C" int srt_split_load_dense_device(int32_t n, int32_t ld, int32_t directed,
-                                           const uint32_t* w, const uint32_t* lat, int32_t row0,
-                                           int32_t nrows, const uint64_t* dem, size_t ldd,
-                                           int64_t arc_cap, int32_t* rowptr, int32_t* tails,
-                                           double* load, int64_t* narcs, double* through,
-                                           uint64_t* totals, void* stream,
-                                           srt_split_load_stats* stats) {
-    if (n < 1 || ld < n || !w || !lat || row0 < 0 || nrows < 1 || (int64_t)row0 + nrows > n ||
-        arc_cap < 0 || !dem || !rowptr || !tails || !load || !through || !totals) {
-        srt_set_error("srt_split_load_dense_device: bad arguments (n = %d, ld = %d, rows [%d, %d))", n,
-                      ld, row0, row0 + nrows);
-        return SRT_E_ARG;
-    }
-    if (n > SRT_DENSE_MAX_N) {
-        srt_set_error("srt_split_load_dense_device: n = %d beyond the dense limit %d", n,
-                      SRT_DENSE_MAX_N);
-        return SRT_E_RANGE;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    srt_split_load_stats local;
-    memset(&local, 0, sizeof(local));
-    int32_t *irp = NULL, *icol = NULL;
-    uint32_t* iw = NULL;
-    int64_t arcs = 0;
-    double ms_ess = 0;
-    int rc = srt_routes_ess_build(n, ld, directed, w, lat, st, &irp, &icol, &iw, &arcs, &ms_ess);
-    if (!rc && narcs) *narcs = arcs;
-    if (!rc && arcs > arc_cap) {
-        srt_set_error("srt_split_load_dense_device: %lld essential arcs, room for %lld",
-                      (long long)arcs, (long long)arc_cap);
-        rc = SRT_E_RANGE;
-    }
-    if (!rc) {
-        TRYHIP(hipMemcpyAsync(rowptr, irp, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-        TRYHIP(hipMemcpyAsync(tails, icol, (size_t)arcs * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-        TRYHIP(hipMemsetAsync(load, 0, (size_t)arcs * sizeof(double), st));
-        TRYHIP(hipMemsetAsync(through, 0, (size_t)n * sizeof(double), st));
-        TRYHIP(hipMemsetAsync(totals, 0, 3 * sizeof(uint64_t), st));
-        rc = srt_split_load_rows(n, nrows, NULL, row0, 0, lat + (size_t)row0 * ld, (size_t)ld, dem, ldd,
-                                 irp, icol, iw, load, through, totals, st, &local);
-    }
-out:
-    srt_routes_ess_free(irp, icol, iw, st);
-    if (!rc && stats) *stats = local;
-    return rc;
-}
-
-extern "C" void srt_split_load_free(srt_split_load* sl) {
-    if (!sl) return;
-    free(sl->tail);
-    free(sl->head);
-    free(sl->load);
-    free(sl->through);
-    free(sl);
-}
-
-/* the arcs (tail, head, load) as the result's, by (tail, head): k of them, which may be 0 */
-static int split_load_set_arcs(srt_split_load* sl, const int32_t* tail, const int32_t* head,
-                               const double* load, size_t k) {
-    const size_t room = k ? k : 1;
-    free(sl->tail);
-    free(sl->head);
-    free(sl->load);
-    sl->tail = (int32_t*)malloc(room * sizeof(int32_t));
-    sl->head = (int32_t*)malloc(room * sizeof(int32_t));
-    sl->load = (double*)malloc(room * sizeof(double));
-    if (!sl->tail || !sl->head || !sl->load) {
-        srt_set_error("srt_build_split_load: out of memory for %zu arcs", k);
-        return SRT_E_NOMEM;
-    }
-    if (k) {
-        memcpy(sl->tail, tail, k * sizeof(int32_t));
-        memcpy(sl->head, head, k * sizeof(int32_t));
-        memcpy(sl->load, load, k * sizeof(double));
-    }
-    sl->narcs = (int64_t)k;
-    return SRT_OK;
-}
-
-/* the positions of a by-head CSR that carry load, as the result's arcs */
-static int split_load_collect(int n, const int32_t* irp, const int32_t* icol, const double* load,
-                              srt_split_load* sl) {
-    const int64_t na = irp[n];
-    std::vector<int64_t> start((size_t)n + 1, 0);
-    int64_t cnt = 0;
-    for (int64_t k = 0; k < na; k++)
-        if (load[k] > 0.0) {
-            start[(size_t)icol[k] + 1]++;
-            cnt++;
-        }
-    for (int v = 0; v < n; v++) start[(size_t)v + 1] += start[v];
-    std::vector<int32_t> tail((size_t)cnt), head((size_t)cnt);
-    std::vector<double> ld((size_t)cnt);
-    /* heads ascend in the outer loop, so each tail's arcs come out by head */
-    for (int t = 0; t < n; t++)
-        for (int64_t k = irp[t]; k < irp[t + 1]; k++)
-            if (load[k] > 0.0) {
-                const int64_t o = start[icol[k]]++;
-                tail[o] = icol[k];
-                head[o] = t;
-                ld[o] = load[k];
-            }
-    return split_load_set_arcs(sl, tail.data(), head.data(), ld.data(), (size_t)cnt);
-}
-
-/* one GPU: the split-load pass over every chunk of the route source's distance rows and the
- * chunk's demand rows, which are built on the device */
-static int split_load_one(const srt_canon* c, const srt_build_opts* opts, int algo,
-                          const ll_demand* dm, srt_split_load* sl) {
-    const int n = c->n;
-    const int nsub = dm->nsub;
-    route_source src = {};
-    dbufs B;
-    B.k = 0;
-    int32_t* dtgt = NULL;
-    int64_t* drowptr = NULL;
-    uint64_t *ddem = NULL, *dval = NULL, *dtot = NULL;
-    double *dload = NULL, *dthrough = NULL;
-    int64_t narcs = 0, max_ent = 0;
-    uint64_t htot[3] = {0, 0, 0};
-    const bool none[3] = {false, false, false};
-    srt_split_load_stats ss;
-    hipStream_t st = NULL;
-    std::vector<int32_t> hirp, hicol;
-    std::vector<double> hload;
-    std::vector<int64_t> rel_rowptr;
-    int rc = SRT_OK;
-    memset(&ss, 0, sizeof(ss));
-    src.rows_only = 1;
-    TRY(route_source_open(&src, c, opts, algo, nsub, dm->verts));
-    st = src.st;
-    narcs = src.narcs;
-    /* beside the source's rows: the load itself, and a u64 demand row per source row */
-    TRY(route_source_chunks(&src, (size_t)narcs * 8, (size_t)n * 8, none));
-    TRY(dalloc(&B, (void**)&ddem, (size_t)src.chunk * n * sizeof(uint64_t)));
-    TRY(dalloc(&B, (void**)&dload, (size_t)narcs * sizeof(double)));
-    TRY(dalloc(&B, (void**)&dthrough, (size_t)n * sizeof(double)));
-    TRY(dalloc(&B, (void**)&dtot, 3 * sizeof(uint64_t)));
-    TRYHIP(hipMemsetAsync(dload, 0, (size_t)narcs * sizeof(double), st));
-    TRYHIP(hipMemsetAsync(dthrough, 0, (size_t)n * sizeof(double), st));
-    TRYHIP(hipMemsetAsync(dtot, 0, 3 * sizeof(uint64_t), st));
-    if (dm->rowptr) { /* room for the COO entries of the largest chunk */
-        for (int r0 = 0; r0 < nsub; r0 += src.chunk) {
-            const int r1 = r0 + src.chunk < nsub ? r0 + src.chunk : nsub;
-            const int64_t e = dm->rowptr[r1] - dm->rowptr[r0];
-            max_ent = e > max_ent ? e : max_ent;
-        }
-        TRY(dalloc(&B, (void**)&drowptr, ((size_t)src.chunk + 1) * sizeof(int64_t)));
-        TRY(dalloc(&B, (void**)&dtgt, (size_t)max_ent * sizeof(int32_t)));
-        TRY(dalloc(&B, (void**)&dval, (size_t)max_ent * sizeof(uint64_t)));
-        rel_rowptr.resize((size_t)src.chunk + 1);
-    }
-    for (int r0 = 0; r0 < nsub; r0 += src.chunk) {
-        TRY(route_source_step(&src, r0));
-        const int cnt = src.cnt;
+    int step(int r0, int cnt, hipStream_t st) {
+        int rc = SRT_OK;
         if (dm->rowptr) { /* the chunk's entries, their row offsets re-based to its first row */
             const int64_t e0 = dm->rowptr[r0], ne = dm->rowptr[r0 + cnt] - e0;
             for (int i = 0; i <= cnt; i++) rel_rowptr[i] = dm->rowptr[r0 + i] - e0;
@@ -3164,29 +2866,93 @@ static int split_load_one(const srt_canon* c, const srt_build_opts* opts, int al
             TRYHIP(hipStreamSynchronize(st)); /* rel_rowptr is reused by the next chunk */
         }
         TRY(srt_link_load_demand_rows(n, cnt, drowptr, dtgt, dval, ddem, (size_t)n, st));
-        TRY(srt_split_load_rows(n, cnt, src.srcs, r0, src.dense, src.dlat,
-                                src.dense ? (size_t)src.ld : (size_t)n, ddem, (size_t)n, src.irp,
-                                src.icol, src.iw, dload, dthrough, dtot, st, &ss));
+    out:
+        return rc;
+    }
+};
+
+/* the positions of a by-head CSR that carry load, as the result's arcs (tail, head, load) */
+template <class T, class R>
+static int load_collect(const char* who, int n, const int32_t* irp, const int32_t* icol,
+                        const T* load, R* res) {
+    const int64_t na = irp[n];
+    std::vector<int64_t> start((size_t)n + 1, 0);
+    int64_t cnt = 0;
+    for (int64_t k = 0; k < na; k++)
+        if (load[k] > 0) {
+            start[(size_t)icol[k] + 1]++;
+            cnt++;
+        }
+    for (int v = 0; v < n; v++) start[(size_t)v + 1] += start[v];
+    const int rc = set_arcs<T>(who, res, (size_t)cnt);
+    if (rc) return rc;
+    /* heads ascend in the outer loop, so each tail's arcs come out by head */
+    for (int t = 0; t < n; t++)
+        for (int64_t k = irp[t]; k < irp[t + 1]; k++)
+            if (load[k] > 0) {
+                const int64_t o = start[icol[k]]++;
+                res->tail[o] = icol[k];
+                res->head[o] = t;
+                res->load[o] = load[k];
+            }
+    return SRT_OK;
+}
+
+/* One GPU: a load pass over every chunk of the route source's rows and the chunk's demand rows.
+ * routes (NULL: no route pass) names the route outputs the pass reads; pass(src, r0, dem, load,
+ * through, totals) adds the rows of the step just taken. *rs: the source's stats at the end. */
+template <class T, class R, class Pass>
+static int load_one(const char* who, const srt_canon* c, const srt_build_opts* opts, int algo,
+                    const ll_demand* dm, const bool* routes, R* res, srt_route_stats* rs,
+                    Pass pass) {
+    const int n = c->n;
+    route_source src = {};
+    demand_feed feed;
+    auto download = [&](void* to, const void* from, size_t bytes) {
+        return hipMemcpyAsync(to, from, bytes, hipMemcpyDeviceToHost, src.st);
+    };
+    dbufs B;
+    B.k = 0;
+    T *dload = NULL, *dthrough = NULL;
+    uint64_t* dtot = NULL;
+    uint64_t htot[3] = {0, 0, 0};
+    std::vector<int32_t> hirp, hicol;
+    std::vector<T> hload;
+    int rc = SRT_OK;
+    src.routes = routes != NULL;
+    for (int i = 0; i < 3; i++) src.want[i] = routes && routes[i];
+    TRY(route_source_open(&src, c, opts, algo, dm->nsub, dm->verts));
+    /* beside the source's rows: the load itself, and a u64 demand row per source row */
+    TRY(route_source_chunks(&src, (size_t)src.narcs * 8, (size_t)n * 8));
+    TRY(feed.open(&B, dm, n, src.chunk));
+    TRY(dalloc(&B, (void**)&dload, (size_t)src.narcs * sizeof(T)));
+    TRY(dalloc(&B, (void**)&dthrough, (size_t)n * sizeof(T)));
+    TRY(dalloc(&B, (void**)&dtot, 3 * sizeof(uint64_t)));
+    TRYHIP(hipMemsetAsync(dload, 0, (size_t)src.narcs * sizeof(T), src.st));
+    TRYHIP(hipMemsetAsync(dthrough, 0, (size_t)n * sizeof(T), src.st));
+    TRYHIP(hipMemsetAsync(dtot, 0, 3 * sizeof(uint64_t), src.st));
+    for (int r0 = 0; r0 < dm->nsub; r0 += src.chunk) {
+        TRY(route_source_step(&src, r0));
+        TRY(feed.step(r0, src.cnt, src.st));
+        TRY(pass(src, r0, (const uint64_t*)feed.ddem, dload, dthrough, dtot));
     }
     hirp.resize((size_t)n + 1);
-    hicol.resize((size_t)(narcs > 0 ? narcs : 1));
-    hload.resize((size_t)(narcs > 0 ? narcs : 1));
-    TRYHIP(hipMemcpyAsync(hirp.data(), src.irp, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (narcs > 0) {
-        TRYHIP(hipMemcpyAsync(hicol.data(), src.icol, (size_t)narcs * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        TRYHIP(hipMemcpyAsync(hload.data(), dload, (size_t)narcs * sizeof(double), hipMemcpyDeviceToHost, st));
+    hicol.resize((size_t)(src.narcs > 0 ? src.narcs : 1));
+    hload.resize((size_t)(src.narcs > 0 ? src.narcs : 1));
+    TRYHIP(download(hirp.data(), src.irp, ((size_t)n + 1) * sizeof(int32_t)));
+    if (src.narcs > 0) {
+        TRYHIP(download(hicol.data(), src.icol, (size_t)src.narcs * sizeof(int32_t)));
+        TRYHIP(download(hload.data(), dload, (size_t)src.narcs * sizeof(T)));
     }
-    TRYHIP(hipMemcpyAsync(sl->through, dthrough, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-    TRYHIP(hipMemcpyAsync(htot, dtot, sizeof(htot), hipMemcpyDeviceToHost, st));
-    TRYHIP(hipStreamSynchronize(st));
-    TRY(split_load_collect(n, hirp.data(), hicol.data(), hload.data(), sl));
-    sl->routed = htot[0];
-    sl->unrouted = htot[1];
-    sl->self_demand = htot[2];
-    sl->ms_tables = src.stats.ms_tables;
-    sl->ms_split = ss.ms_split;
-    sl->tied_pairs = ss.tied_pairs;
-    sl->forms = ss.forms;
+    TRYHIP(download(res->through, dthrough, (size_t)n * sizeof(T)));
+    TRYHIP(download(htot, dtot, sizeof(htot)));
+    TRYHIP(hipStreamSynchronize(src.st));
+    TRY(load_collect(who, n, hirp.data(), hicol.data(), hload.data(), res));
+    res->routed = htot[0];
+    res->unrouted = htot[1];
+    res->self_demand = htot[2];
+    res->ms_tables = src.stats.ms_tables;
+    *rs = src.stats;
 out:
     route_source_close(&src);
     dfree(&B);
@@ -3194,10 +2960,11 @@ out:
 }
 
 /* direct mode (topology.c:1816-1858): every pair is its own edge, so load(s -> t) = c(s, t) */
-static int split_load_direct(const srt_edges* g, const ll_demand* dm, srt_split_load* sl) {
+template <class T, class R>
+static int load_direct(const char* who, const srt_edges* g, const ll_demand* dm, R* res) {
     const int n = g->n;
     std::vector<int32_t> tail, head;
-    std::vector<double> load;
+    std::vector<T> load;
     std::vector<uint64_t> row;
     if (dm->rowptr) row.assign((size_t)n, 0);
     for (int32_t i = 0; i < dm->nsub; i++) {
@@ -3209,74 +2976,106 @@ static int split_load_direct(const srt_edges* g, const ll_demand* dm, srt_split_
             if (dm->rowptr) row[t] = 0;
             if (!cst) continue;
             if (t == s) {
-                sl->self_demand += cst;
+                res->self_demand += cst;
                 continue;
             }
-            sl->routed += cst;
+            res->routed += cst;
             tail.push_back(s);
             head.push_back(t);
-            load.push_back((double)cst);
+            load.push_back((T)cst);
         }
     }
-    return split_load_set_arcs(sl, tail.data(), head.data(), load.data(), tail.size());
+    return set_arcs<T>(who, res, tail.size(), tail.data(), head.data(), load.data());
+}
+
+/* The entry of the two srt_build_*_load: post_entry with the demand as its check -- parsed, its
+ * total below `limit` where the load words could not hold more exactly (0: no limit beyond u64),
+ * then the empty result --, the direct load, and run(c, algo, dm, res) as the pass. */
+template <class T, class R, class Run>
+static int load_entry(const char* who, const char* pass, uint64_t limit, const srt_edges* g,
+                      const srt_build_opts* opts, int32_t nsrc, const int32_t* srcs, int64_t ndem,
+                      const int32_t* dsrc, const int32_t* dtgt, const uint64_t* dval, R** out,
+                      Run run) {
+    if (out) *out = NULL;
+    ll_demand dm = {0, NULL, NULL, NULL, NULL};
+    std::vector<int32_t> dverts;
+    std::vector<int64_t> rowptr;
+    R* res = NULL;
+    const int rc = post_entry(
+        who, pass, g, opts, g && g->n > 0 && out, NULL, 0,
+        [&](int* nsub) {
+            uint64_t total = 0;
+            const int drc = ll_demand_parse(who, g->n, nsrc, srcs, ndem, dsrc, dtgt, dval, &dm,
+                                            &dverts, &rowptr, &total);
+            if (drc) return drc;
+            if (limit && total >= limit) { /* every c and every total then converts to f64 exactly */
+                srt_set_error("%s: a total demand of %llu (2^53 or more) is not exact in f64", who,
+                              (unsigned long long)total);
+                return (int)SRT_E_RANGE;
+            }
+            res = load_new<T, R>(who, g->n);
+            *nsub = dm.nsub;
+            return (int)(res ? SRT_OK : SRT_E_NOMEM);
+        },
+        [&] { return load_direct<T>(who, g, &dm, res); },
+        [&](const srt_canon* c, int algo) { return run(c, algo, &dm, res); });
+    if (rc)
+        load_free(res);
+    else
+        *out = res;
+    return rc;
+}
+
+extern "C" int srt_build_link_load(const srt_edges* g, const srt_build_opts* opts, int32_t nsrc,
+                                   const int32_t* srcs, int64_t ndem, const int32_t* dsrc,
+                                   const int32_t* dtgt, const uint64_t* dval, srt_link_load** out) {
+    const char* who = "srt_build_link_load";
+    const int rc = load_entry<uint64_t>(
+        who, "route pass", 0, g, opts, nsrc, srcs, ndem, dsrc, dtgt, dval, out,
+        [&](const srt_canon* c, int algo, const ll_demand* dm, srt_link_load* ll) {
+            static const bool routes[3] = {true, false, true}; /* pred and hops */
+            srt_route_stats rs;
+            ll->ms_load = 0;
+            ll->max_hops = 0;
+            ll->forms = 0;
+            const int lrc = load_one<uint64_t>(
+                who, c, opts, algo, dm, routes, ll, &rs,
+                [&](const route_source& src, int r0, const uint64_t* dem, uint64_t* load,
+                    uint64_t* through, uint64_t* totals) {
+                    return srt_link_load_rows(c->n, src.cnt, src.srcs, r0, src.dout[0], src.dout[2],
+                                              (size_t)c->n, dem, (size_t)c->n, src.irp, src.icol,
+                                              load, through, src.sorted, totals, src.st,
+                                              &ll->max_hops, &ll->forms, &ll->ms_load);
+                });
+            if (!lrc) ll->ms_routes = rs.ms_routes;
+            return lrc;
+        });
+    /* direct mode: every loaded arc is a route of one hop */
+    if (!rc && !(opts ? opts->use_shortest_path : 1)) (*out)->max_hops = (*out)->narcs ? 1 : 0;
+    return rc;
 }
 
 extern "C" int srt_build_split_load(const srt_edges* g, const srt_build_opts* opts, int32_t nsrc,
                                     const int32_t* srcs, int64_t ndem, const int32_t* dsrc,
                                     const int32_t* dtgt, const uint64_t* dval,
                                     srt_split_load** out) {
-    if (out) *out = NULL;
-    if (!g || g->n <= 0 || !out) {
-        srt_set_error("srt_build_split_load: null argument");
-        return SRT_E_ARG;
-    }
-    last_row_chunks.store(0, std::memory_order_relaxed);
-    const int n = g->n;
-    ll_demand dm = {0, NULL, NULL, NULL, NULL};
-    std::vector<int32_t> dverts;
-    std::vector<int64_t> rowptr;
-    uint64_t total = 0;
-    int rc = ll_demand_parse("srt_build_split_load", n, nsrc, srcs, ndem, dsrc, dtgt, dval, &dm,
-                             &dverts, &rowptr, &total);
-    if (rc) return rc;
-    if (total >= (uint64_t)1 << 53) { /* every c and every total then converts to f64 exactly */
-        srt_set_error("srt_build_split_load: a total demand of %llu (2^53 or more) is not exact in "
-                      "f64", (unsigned long long)total);
-        return SRT_E_RANGE;
-    }
-    srt_split_load* sl = (srt_split_load*)calloc(1, sizeof(srt_split_load));
-    if (sl) sl->through = (double*)calloc((size_t)n, sizeof(double));
-    if (!sl || !sl->through) {
-        srt_split_load_free(sl);
-        srt_set_error("srt_build_split_load: out of memory");
-        return SRT_E_NOMEM;
-    }
-    const int use_sp = opts ? opts->use_shortest_path : 1;
-    if (!use_sp) {
-        int32_t* const none[3] = {NULL, NULL, NULL};
-        rc = routes_direct(g, 0, NULL, none); /* the completeness check and its error */
-        if (!rc) rc = split_load_direct(g, &dm, sl);
-    } else if (dm.nsub == 0) {
-        rc = split_load_set_arcs(sl, NULL, NULL, NULL, 0); /* no demand: nothing to route */
-    } else if (srt_device_count() < 1) {
-        srt_set_error("srt_build_split_load: no HIP device");
-        rc = SRT_E_DEVICE;
-    } else {
-        rc = with_canon(g, opts, 1, [&](const srt_canon* c, int algo, double) {
-            if (c->wide) {
-                srt_set_error("srt_build_split_load: shortest-path latencies may pass the u32 range "
-                              "(bound %llu quanta of %llu ns); the split-load pass reads u32 rows "
-                              "only", (unsigned long long)c->dist_bound,
-                              (unsigned long long)c->quantum_ns);
-                return (int)SRT_E_RANGE;
-            }
-            return split_load_one(c, opts, algo, &dm, sl);
+    const char* who = "srt_build_split_load";
+    return load_entry<double>(
+        who, "split-load pass", (uint64_t)1 << 53, g, opts, nsrc, srcs, ndem, dsrc, dtgt, dval, out,
+        [&](const srt_canon* c, int algo, const ll_demand* dm, srt_split_load* sl) {
+            srt_route_stats rs;
+            srt_split_load_stats ss = {};
+            const int lrc = load_one<double>(
+                who, c, opts, algo, dm, NULL, sl, &rs,
+                [&](const route_source& src, int r0, const uint64_t* dem, double* load,
+                    double* through, uint64_t* totals) {
+                    return srt_split_load_rows(c->n, src.cnt, src.srcs, r0, src.dense, src.dlat,
+                                               src.ldd(), dem, (size_t)c->n, src.irp, src.icol,
+                                               src.iw, load, through, totals, src.st, &ss);
+                });
+            sl->ms_split = ss.ms_split;
+            sl->tied_pairs = ss.tied_pairs;
+            sl->forms = ss.forms;
+            return lrc;
         });
-    }
-    if (rc) {
-        srt_split_load_free(sl);
-        return rc;
-    }
-    *out = sl;
-    return SRT_OK;
 }

@@ -21,7 +21,7 @@
  * Like the route pass it reads u32 distance rows and an in-arc CSR (here with the arcs'
  * reliabilities), whichever build made the rows; the front ends are the same two.
  */
-#include "srt_device.h"
+#include "srt_pass.h"
 
 #include <string.h>
 
@@ -32,7 +32,6 @@
  * route pass's RT_WAVE_ARCS and RT_GROUP) */
 #define EV_WAVE_ARCS 32
 #define EV_GROUP 4
-#define EV_SCRATCH_BYTES ((size_t)8 << 30)
 
 /* the bitmaps (done, fresh, exposed): one 64-bit word per 64 targets each */
 static size_t ev_bitmap_bytes(int n) { return 3 * (size_t)srt_ceil_div(n, 64) * 8; }
@@ -340,16 +339,6 @@ __global__ __launch_bounds__(EV_THREADS) void envelope_kernel(
     }
 }
 
-#define EV_TRY(x)                                                                              \
-    do {                                                                                       \
-        hipError_t e_ = (x);                                                                   \
-        if (e_ != hipSuccess) {                                                                \
-            srt_set_error("HIP error %s at %s:%d", hipGetErrorString(e_), __FILE__, __LINE__); \
-            rc = SRT_E_DEVICE;                                                                 \
-            goto out;                                                                          \
-        }                                                                                      \
-    } while (0)
-
 /* The envelope pass over nrows distance rows (see envelope_kernel); either output may be NULL.
  * Adds the HIP-event time, the counts, the sweeps and the staging forms to *stats (the caller
  * zeroes it); returns after the stream. */
@@ -372,52 +361,39 @@ int srt_envelope_rows(int n, int nrows, const int32_t* srcs, int src_begin, int 
     /* per-block scratch: the hint row and the row of an output that is NULL (the 8-byte words
      * first: aligned); the grid shrinks to fit */
     const size_t per_block = (size_t)n * (8 * ((lo ? 0 : 1) + (hi ? 0 : 1)) + 4);
-    const int cus = srt_cu_count();
-    int grid = lds > 76 * 1024 ? cus : 2 * cus; /* workgroups the LDS lets a CU hold */
-    if ((size_t)grid * per_block > EV_SCRATCH_BYTES)
-        grid = (int)(EV_SCRATCH_BYTES / per_block) > 0 ? (int)(EV_SCRATCH_BYTES / per_block) : 1;
-    grid = nrows < grid ? nrows : grid;
-    char* ws = NULL;
-    unsigned long long* dstat = NULL; /* the three counts, then max_sweeps and forms (32 bits each) */
+    const int grid = srt_pass_grid(lds, per_block, nrows, false);
+    srt_pass_scratch sc;
     double *ws_lo = NULL, *ws_hi = NULL;
     int32_t* ws_hint = NULL;
+    /* the three counts, then max_sweeps and forms (32 bits each) */
     unsigned long long hstat[4] = {0, 0, 0, 0};
     double ms = 0;
     srt_event_span span;
     int rc = span.begin(st);
     if (rc) return rc;
-    if (srt_malloc_async((void**)&ws, (size_t)grid * per_block, st) != hipSuccess) {
-        (void)hipGetLastError();
-        srt_set_error("envelope pass: scratch of %zu MiB failed", ((size_t)grid * per_block) >> 20);
-        return SRT_E_NOMEM;
-    }
+    rc = sc.open("envelope pass", st, (size_t)grid * per_block, sizeof(hstat));
+    if (rc) return rc;
+    char* const ws = sc.ws;
+    unsigned long long* const dstat = (unsigned long long*)sc.dstat;
     if (!lo) ws_lo = (double*)ws;
     if (!hi) ws_hi = (double*)ws + (lo ? 0 : (size_t)grid * n);
     ws_hint = (int32_t*)((double*)ws + (size_t)grid * n * ((lo ? 0 : 1) + (hi ? 0 : 1)));
-    EV_TRY(srt_malloc_async((void**)&dstat, sizeof(hstat), st));
-    EV_TRY(hipMemsetAsync(dstat, 0, sizeof(hstat), st));
     if (form == 1) {
-        EV_TRY(hipFuncSetAttribute((const void*)envelope_kernel<1>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        SRT_PASS_TRY(hipFuncSetAttribute((const void*)envelope_kernel<1>,
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         envelope_kernel<1><<<grid, EV_THREADS, lds, st>>>(
             n, nrows, srcs, src_begin, by_src, D, ldd, irp, icol, iw, ir, lo, hi, ldo, ws_lo, ws_hi,
             ws_hint, dstat, (int32_t*)(dstat + 3), (uint32_t*)(dstat + 3) + 1);
     } else {
-        EV_TRY(hipFuncSetAttribute((const void*)envelope_kernel<3>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        SRT_PASS_TRY(hipFuncSetAttribute((const void*)envelope_kernel<3>,
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         envelope_kernel<3><<<grid, EV_THREADS, lds, st>>>(
             n, nrows, srcs, src_begin, by_src, D, ldd, irp, icol, iw, ir, lo, hi, ldo, ws_lo, ws_hi,
             ws_hint, dstat, (int32_t*)(dstat + 3), (uint32_t*)(dstat + 3) + 1);
     }
-    EV_TRY(hipGetLastError());
-    EV_TRY(hipMemcpyAsync(hstat, dstat, sizeof(hstat), hipMemcpyDeviceToHost, st));
+    SRT_PASS_TRY(hipGetLastError());
 out:
-    if (ws) (void)hipFreeAsync(ws, st);
-    if (dstat) (void)hipFreeAsync(dstat, st);
-    if (hipStreamSynchronize(st) != hipSuccess && !rc) {
-        srt_set_error("envelope pass: the kernel failed (%s)", hipGetErrorString(hipGetLastError()));
-        rc = SRT_E_DEVICE;
-    }
+    rc = sc.finish(rc, hstat);
     if (!rc) rc = span.end(st, &ms);
     if (!rc && stats) {
         const int32_t sweeps = (int32_t)(uint32_t)hstat[3];
@@ -463,9 +439,9 @@ int srt_envelope_ess_rel(int n, int ld, int64_t arcs, const int32_t* irp, const 
     int rc = span.begin(st);
     if (rc) return rc;
     const int grid = srt_ceil_div(arcs, 256) < 8192 ? (arcs ? srt_ceil_div(arcs, 256) : 1) : 8192;
-    EV_TRY(srt_malloc_async((void**)ir, ((size_t)arcs + 1) * sizeof(double), st));
+    SRT_PASS_TRY(srt_malloc_async((void**)ir, ((size_t)arcs + 1) * sizeof(double), st));
     ev_ess_rel_kernel<<<grid, 256, 0, st>>>(n, ld, (int)arcs, irp, icol, r, *ir);
-    EV_TRY(hipGetLastError());
+    SRT_PASS_TRY(hipGetLastError());
     rc = span.end(st, ms);
 out:
     if (rc && *ir) {

@@ -14,7 +14,7 @@
  * deepest first: the targets are ordered by hop count once per row (a counting sort inside the
  * workgroup), then every level is one contiguous segment of that order and costs one barrier.
  */
-#include "srt_device.h"
+#include "srt_pass.h"
 
 #include <string.h>
 
@@ -29,7 +29,6 @@
 #define LL_AGG 4
 /* hop levels counted in LDS by rows too long for LDS flow words; deeper rows count in scratch */
 #define LL_BIG_LEVELS 4096
-#define LL_SCRATCH_BYTES ((size_t)8 << 30)
 #define LL_MAX_N (1 << 22)
 
 typedef unsigned long long ull;
@@ -436,24 +435,6 @@ __global__ __launch_bounds__(256) void ll_demand_kernel(int n, int nrows, int un
     }
 }
 
-static int ll_cus(void) {
-    int cus = 256, dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-        cus = prop.multiProcessorCount;
-    return cus;
-}
-
-#define LL_TRY(x)                                                                              \
-    do {                                                                                       \
-        hipError_t e_ = (x);                                                                   \
-        if (e_ != hipSuccess) {                                                                \
-            srt_set_error("HIP error %s at %s:%d", hipGetErrorString(e_), __FILE__, __LINE__); \
-            rc = SRT_E_DEVICE;                                                                 \
-            goto out;                                                                          \
-        }                                                                                      \
-    } while (0)
-
 int srt_link_load_demand_rows(int n, int nrows, const int64_t* rowptr, const int32_t* tgt,
                               const uint64_t* val, uint64_t* dem, size_t ldd, hipStream_t st) {
     if (nrows <= 0) return SRT_OK;
@@ -469,8 +450,9 @@ int srt_link_load_demand_rows(int n, int nrows, const int64_t* rowptr, const int
 }
 
 /* The load pass over nrows rows (see link_load_kernel): adds into load, through and totals (the
- * caller zeroes them); sorted != 0 promises in-lists with ascending tails; raises *max_hops, ors the flow forms taken into *forms, adds the HIP-event
- * time of the pass to *ms. Returns after the stream. */
+ * caller zeroes them); sorted != 0 promises in-lists with ascending tails; raises *max_hops, ors
+ * the flow forms taken into *forms, adds the HIP-event time of the pass to *ms. Returns after the
+ * stream. */
 int srt_link_load_rows(int n, int nrows, const int32_t* srcs, int src_begin, const int32_t* pred,
                        const int32_t* hops, size_t ldp, const uint64_t* dem, size_t ldd,
                        const int32_t* irp, const int32_t* icol, uint64_t* load, uint64_t* through,
@@ -491,34 +473,23 @@ int srt_link_load_rows(int n, int nrows, const int32_t* srcs, int src_begin, con
     const bool gflow = n > max2; /* some row may take form 3 */
     /* per workgroup: order (n int32), lvl (n + 1 u32), the form-3 flow words (n u64) */
     const size_t per_block = (size_t)n * 4 + ((size_t)n + 1) * 4 + (gflow ? (size_t)n * 8 : 0);
-    const int cus = ll_cus();
-    int grid = lds > 76 * 1024 ? cus : 2 * cus; /* workgroups the LDS lets a CU hold */
-    if ((size_t)grid * per_block > LL_SCRATCH_BYTES)
-        grid = (int)(LL_SCRATCH_BYTES / per_block) > 0 ? (int)(LL_SCRATCH_BYTES / per_block) : 1;
-    grid = nrows < grid ? nrows : grid;
-    char* ws = NULL;
-    int32_t* dstat = NULL;
-    hipEvent_t ev[2] = {NULL, NULL};
-    int rc = SRT_OK;
+    const int grid = srt_pass_grid(lds, per_block, nrows, false);
+    srt_pass_scratch sc;
+    srt_event_span span;
     int32_t hstat[2] = {0, 0};
-    float span = 0;
+    double span_ms = 0;
     /* the u64 words first (aligned), then lvl, then order */
     const size_t off_lvl = gflow ? (size_t)grid * n * 8 : 0;
     const size_t off_order = off_lvl + (size_t)grid * ((size_t)n + 1) * 4;
-    if (srt_malloc_async((void**)&ws, (size_t)grid * per_block, st) != hipSuccess) {
-        (void)hipGetLastError();
-        srt_set_error("link load: scratch of %zu MiB failed", ((size_t)grid * per_block) >> 20);
-        return SRT_E_NOMEM;
-    }
-    LL_TRY(hipEventCreate(&ev[0]));
-    LL_TRY(hipEventCreate(&ev[1]));
-    LL_TRY(srt_malloc_async((void**)&dstat, 2 * sizeof(int32_t), st));
-    LL_TRY(hipMemsetAsync(dstat, 0, 2 * sizeof(int32_t), st));
-    LL_TRY(hipFuncSetAttribute((const void*)link_load_kernel<true>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    LL_TRY(hipFuncSetAttribute((const void*)link_load_kernel<false>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    LL_TRY(hipEventRecord(ev[0], st));
+    int rc = sc.open("link load", st, (size_t)grid * per_block, sizeof(hstat));
+    if (rc) return rc;
+    char* const ws = sc.ws;
+    int32_t* const dstat = (int32_t*)sc.dstat;
+    SRT_PASS_TRY(hipFuncSetAttribute((const void*)link_load_kernel<true>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    SRT_PASS_TRY(hipFuncSetAttribute((const void*)link_load_kernel<false>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if ((rc = span.begin(st)) != SRT_OK) goto out;
     if (sorted)
         link_load_kernel<true><<<grid, LL_THREADS, lds, st>>>(
             n, nrows, srcs, src_begin, pred, hops, ldp, (const ull*)dem, ldd, irp, icol, (ull*)load,
@@ -529,26 +500,15 @@ int srt_link_load_rows(int n, int nrows, const int32_t* srcs, int src_begin, con
             n, nrows, srcs, src_begin, pred, hops, ldp, (const ull*)dem, ldd, irp, icol, (ull*)load,
             (ull*)through, (ull*)totals, (int32_t*)(ws + off_order), (uint32_t*)(ws + off_lvl),
             gflow ? (ull*)ws : NULL, (int)(lds / 4), dstat, (uint32_t*)dstat + 1);
-    LL_TRY(hipGetLastError());
-    LL_TRY(hipEventRecord(ev[1], st));
-    LL_TRY(hipMemcpyAsync(hstat, dstat, sizeof(hstat), hipMemcpyDeviceToHost, st));
+    SRT_PASS_TRY(hipGetLastError());
+    rc = span.stop(st); /* the span ends with the kernel, before the stat words travel */
 out:
-    if (ws) (void)hipFreeAsync(ws, st);
-    if (dstat) (void)hipFreeAsync(dstat, st);
-    if (hipStreamSynchronize(st) != hipSuccess && !rc) {
-        srt_set_error("link load: the kernel failed (%s)", hipGetErrorString(hipGetLastError()));
-        rc = SRT_E_DEVICE;
-    }
-    if (!rc && hipEventElapsedTime(&span, ev[0], ev[1]) != hipSuccess) {
-        (void)hipGetLastError();
-        span = 0;
-    }
-    for (hipEvent_t e : ev)
-        if (e) (void)hipEventDestroy(e);
+    rc = sc.finish(rc, hstat);
+    if (!rc) rc = span.read(&span_ms);
     if (!rc) {
         if (max_hops && hstat[0] > *max_hops) *max_hops = hstat[0];
         if (forms) *forms |= hstat[1];
-        if (ms) *ms += span;
+        if (ms) *ms += span_ms;
     }
     return rc;
 }

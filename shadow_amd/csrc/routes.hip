@@ -15,7 +15,7 @@
  * in-arc CSR compacted here from the public w and lat matrices -- an arc (u, t), u != t, with
  * w[u][t] == lat[u][t]; only those can be tight.
  */
-#include "srt_device.h"
+#include "srt_pass.h"
 
 #include <string.h>
 
@@ -28,8 +28,7 @@
 #define RT_WAVE_ARCS 32
 /* such lists a wave reads at the same time */
 #define RT_GROUP 4
-/* most scratch of one pass (the grid shrinks to fit), and the largest n it takes */
-#define RT_SCRATCH_BYTES ((size_t)8 << 30)
+/* the largest n the pass takes */
 #define RT_MAX_N (1 << 22)
 
 static size_t rt_row_bytes(int n, int form) {
@@ -279,16 +278,6 @@ __global__ __launch_bounds__(RT_THREADS) void routes_kernel(
     if (tid == 0 && form_mask) atomicOr(forms, form_mask);
 }
 
-#define RT_TRY(x)                                                                              \
-    do {                                                                                       \
-        hipError_t e_ = (x);                                                                   \
-        if (e_ != hipSuccess) {                                                                \
-            srt_set_error("HIP error %s at %s:%d", hipGetErrorString(e_), __FILE__, __LINE__); \
-            rc = SRT_E_DEVICE;                                                                 \
-            goto out;                                                                          \
-        }                                                                                      \
-    } while (0)
-
 /* The route pass over nrows distance rows (see routes_kernel); any output may be NULL. Adds the
  * deepest route to *max_hops and the staging forms taken to *forms; returns after the stream. */
 int srt_routes_rows(int n, int nrows, const int32_t* srcs, int src_begin, int by_src,
@@ -308,37 +297,28 @@ int srt_routes_rows(int n, int nrows, const int32_t* srcs, int src_begin, int by
     const int nform = n <= srt_routes_stage_max_n(1) ? 1 : n <= srt_routes_stage_max_n(2) ? 2 : 3;
     const size_t lds = rt_row_bytes(n, nform);
     /* per-block scratch: the predecessor row where that output is NULL, the jump words of forms 2
-     * and 3; the grid shrinks where it would pass RT_SCRATCH_BYTES */
+     * and 3; the grid shrinks where it would pass SRT_PASS_SCRATCH_BYTES */
     const size_t per_block = (size_t)n * ((pred ? 0 : sizeof(int32_t)) + (nform == 1 ? 0 : 8));
-    const int cus = srt_cu_count();
-    int grid = lds > 76 * 1024 ? cus : 2 * cus; /* workgroups the LDS lets a CU hold */
-    if (per_block && (size_t)grid * per_block > RT_SCRATCH_BYTES)
-        grid = (int)(RT_SCRATCH_BYTES / per_block) > 0 ? (int)(RT_SCRATCH_BYTES / per_block) : 1;
-    grid = nrows < grid ? nrows : grid;
-    char* ws = NULL;
-    int32_t* dstat = NULL;
+    const int grid = srt_pass_grid(lds, per_block, nrows, false);
+    srt_pass_scratch sc;
     int32_t* ws_pred = NULL;
     unsigned long long* ws_jump = NULL;
-    int rc = SRT_OK;
     int32_t hstat[2] = {0, 0};
-    if (per_block && srt_malloc_async((void**)&ws, (size_t)grid * per_block, st) != hipSuccess) {
-        (void)hipGetLastError();
-        srt_set_error("route pass: scratch of %zu MiB failed", ((size_t)grid * per_block) >> 20);
-        return SRT_E_NOMEM;
-    }
+    int rc = sc.open("route pass", st, (size_t)grid * per_block, sizeof(hstat));
+    if (rc) return rc;
+    char* const ws = sc.ws;
+    int32_t* const dstat = (int32_t*)sc.dstat;
     if (nform != 1) ws_jump = (unsigned long long*)ws; /* the 8-byte words first: aligned */
     if (!pred) ws_pred = (int32_t*)(ws + (nform == 1 ? 0 : (size_t)grid * n * 8));
-    RT_TRY(srt_malloc_async((void**)&dstat, 2 * sizeof(int32_t), st));
-    RT_TRY(hipMemsetAsync(dstat, 0, 2 * sizeof(int32_t), st));
     if (nform == 1) {
-        RT_TRY(hipFuncSetAttribute((const void*)routes_kernel<1>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        SRT_PASS_TRY(hipFuncSetAttribute((const void*)routes_kernel<1>,
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         routes_kernel<1><<<grid, RT_THREADS, lds, st>>>(n, nrows, srcs, src_begin, by_src, D, ldd, irp,
                                                         icol, iw, pred, first, hops, ldo, ws_pred,
                                                         ws_jump, dstat, (uint32_t*)dstat + 1);
     } else if (nform == 2) {
-        RT_TRY(hipFuncSetAttribute((const void*)routes_kernel<2>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        SRT_PASS_TRY(hipFuncSetAttribute((const void*)routes_kernel<2>,
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         routes_kernel<2><<<grid, RT_THREADS, lds, st>>>(n, nrows, srcs, src_begin, by_src, D, ldd, irp,
                                                         icol, iw, pred, first, hops, ldo, ws_pred,
                                                         ws_jump, dstat, (uint32_t*)dstat + 1);
@@ -347,15 +327,9 @@ int srt_routes_rows(int n, int nrows, const int32_t* srcs, int src_begin, int by
                                                       icol, iw, pred, first, hops, ldo, ws_pred,
                                                       ws_jump, dstat, (uint32_t*)dstat + 1);
     }
-    RT_TRY(hipGetLastError());
-    RT_TRY(hipMemcpyAsync(hstat, dstat, sizeof(hstat), hipMemcpyDeviceToHost, st));
+    SRT_PASS_TRY(hipGetLastError());
 out:
-    if (ws) (void)hipFreeAsync(ws, st);
-    if (dstat) (void)hipFreeAsync(dstat, st);
-    if (hipStreamSynchronize(st) != hipSuccess && !rc) {
-        srt_set_error("route pass: the kernel failed (%s)", hipGetErrorString(hipGetLastError()));
-        rc = SRT_E_DEVICE;
-    }
+    rc = sc.finish(rc, hstat);
     if (!rc) {
         if (max_hops && hstat[0] > *max_hops) *max_hops = hstat[0];
         if (forms) *forms |= hstat[1];
@@ -462,19 +436,19 @@ int srt_routes_ess_build(int n, int ld, int directed, const uint32_t* w, const u
     if (rc) return rc;
     const int grid = srt_ceil_div(n, 4) < 4096 ? srt_ceil_div(n, 4) : 4096;
     /* cnt: n counters, then n cursors */
-    RT_TRY(srt_malloc_async((void**)&cnt, 2 * (size_t)n * sizeof(int32_t), st));
-    RT_TRY(srt_malloc_async((void**)irp, ((size_t)n + 1) * sizeof(int32_t), st));
-    RT_TRY(hipMemsetAsync(cnt, 0, 2 * (size_t)n * sizeof(int32_t), st));
+    SRT_PASS_TRY(srt_malloc_async((void**)&cnt, 2 * (size_t)n * sizeof(int32_t), st));
+    SRT_PASS_TRY(srt_malloc_async((void**)irp, ((size_t)n + 1) * sizeof(int32_t), st));
+    SRT_PASS_TRY(hipMemsetAsync(cnt, 0, 2 * (size_t)n * sizeof(int32_t), st));
     rt_ess_kernel<false><<<grid, 256, 0, st>>>(n, ld, directed, w, lat, cnt, NULL, NULL, NULL, NULL);
-    RT_TRY(hipGetLastError());
+    SRT_PASS_TRY(hipGetLastError());
     rt_scan_kernel<<<1, 1024, 0, st>>>(n, cnt, *irp, cnt + n);
-    RT_TRY(hipGetLastError());
-    RT_TRY(hipMemcpyAsync(&total, *irp + n, sizeof(total), hipMemcpyDeviceToHost, st));
-    RT_TRY(hipStreamSynchronize(st));
-    RT_TRY(srt_malloc_async((void**)icol, ((size_t)total + 1) * sizeof(int32_t), st));
-    RT_TRY(srt_malloc_async((void**)iw, ((size_t)total + 1) * sizeof(uint32_t), st));
+    SRT_PASS_TRY(hipGetLastError());
+    SRT_PASS_TRY(hipMemcpyAsync(&total, *irp + n, sizeof(total), hipMemcpyDeviceToHost, st));
+    SRT_PASS_TRY(hipStreamSynchronize(st));
+    SRT_PASS_TRY(srt_malloc_async((void**)icol, ((size_t)total + 1) * sizeof(int32_t), st));
+    SRT_PASS_TRY(srt_malloc_async((void**)iw, ((size_t)total + 1) * sizeof(uint32_t), st));
     rt_ess_kernel<true><<<grid, 256, 0, st>>>(n, ld, directed, w, lat, NULL, *irp, cnt + n, *icol, *iw);
-    RT_TRY(hipGetLastError());
+    SRT_PASS_TRY(hipGetLastError());
     *arcs = total;
     rc = span.end(st, ms);
 out:

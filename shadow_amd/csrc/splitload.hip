@@ -22,7 +22,7 @@
  * CSR position) and through with f64 atomics in device memory, so two runs may differ in the last
  * bits where the partial sums are not exact.
  */
-#include "srt_device.h"
+#include "srt_pass.h"
 
 #include <string.h>
 
@@ -33,7 +33,6 @@
  * route pass's RT_WAVE_ARCS and RT_GROUP) */
 #define SL_WAVE_ARCS 32
 #define SL_GROUP 4
-#define SL_SCRATCH_BYTES ((size_t)8 << 30)
 
 typedef unsigned long long ull;
 
@@ -470,16 +469,6 @@ __global__ __launch_bounds__(SL_THREADS) void split_load_kernel(
     }
 }
 
-#define SL_TRY(x)                                                                              \
-    do {                                                                                       \
-        hipError_t e_ = (x);                                                                   \
-        if (e_ != hipSuccess) {                                                                \
-            srt_set_error("HIP error %s at %s:%d", hipGetErrorString(e_), __FILE__, __LINE__); \
-            rc = SRT_E_DEVICE;                                                                 \
-            goto out;                                                                          \
-        }                                                                                      \
-    } while (0)
-
 template <int FORM>
 static hipError_t sl_launch(int grid, size_t lds, hipStream_t st, int n, int nrows,
                             const int32_t* srcs, int src_begin, int by_src, const uint32_t* D,
@@ -523,13 +512,9 @@ int srt_split_load_rows(int n, int nrows, const int32_t* srcs, int src_begin, in
     const size_t per_block = (size_t)n * (8 + (form != 1 ? 12 : 0));
     /* one workgroup a CU: the kernel takes 128 VGPRs, so its 16 waves fill the CU's four SIMDs
      * (4 waves each) whatever LDS is left; a second one would only queue and double the scratch */
-    int grid = srt_cu_count();
-    if ((size_t)grid * per_block > SL_SCRATCH_BYTES)
-        grid = (int)(SL_SCRATCH_BYTES / per_block) > 0 ? (int)(SL_SCRATCH_BYTES / per_block) : 1;
-    grid = nrows < grid ? nrows : grid;
-    char* ws = NULL;
-    ull* dstat = NULL; /* the tied pairs, then max_sweeps and forms (32 bits each) */
-    ull hstat[2] = {0, 0};
+    const int grid = srt_pass_grid(lds, per_block, nrows, true);
+    srt_pass_scratch sc;
+    ull hstat[2] = {0, 0}; /* the tied pairs, then max_sweeps and forms (32 bits each) */
     double* ws_inflow = NULL;
     uint32_t *ws_dmin = NULL, *ws_cnt = NULL, *ws_kids = NULL;
     double ms = 0;
@@ -537,13 +522,11 @@ int srt_split_load_rows(int n, int nrows, const int32_t* srcs, int src_begin, in
     srt_event_span span;
     int rc = span.begin(st);
     if (rc) return rc;
-    if (srt_malloc_async((void**)&ws, (size_t)grid * per_block, st) != hipSuccess) {
-        (void)hipGetLastError();
-        srt_set_error("split load: scratch of %zu MiB failed", ((size_t)grid * per_block) >> 20);
-        return SRT_E_NOMEM;
-    }
+    rc = sc.open("split load", st, (size_t)grid * per_block, sizeof(hstat));
+    if (rc) return rc;
+    ull* const dstat = (ull*)sc.dstat;
     {
-        char* p = ws;
+        char* p = sc.ws;
         if (form != 1) {
             ws_inflow = (double*)p;
             p += (size_t)grid * n * 8;
@@ -553,22 +536,14 @@ int srt_split_load_rows(int n, int nrows, const int32_t* srcs, int src_begin, in
         ws_dmin = (uint32_t*)p;
         ws_cnt = ws_dmin + (size_t)grid * n;
     }
-    SL_TRY(srt_malloc_async((void**)&dstat, sizeof(hstat), st));
-    SL_TRY(hipMemsetAsync(dstat, 0, sizeof(hstat), st));
 #define SL_ARGS                                                                                    \
     grid, lds, st, n, nrows, srcs, src_begin, by_src, D, ldd, (const ull*)dem, ldc, irp, icol, iw, \
         load, through, (ull*)totals, ws_dmin, ws_cnt, ws_kids, ws_inflow, dstat
     le = form == 1 ? sl_launch<1>(SL_ARGS) : form == 2 ? sl_launch<2>(SL_ARGS) : sl_launch<3>(SL_ARGS);
 #undef SL_ARGS
-    SL_TRY(le);
-    SL_TRY(hipMemcpyAsync(hstat, dstat, sizeof(hstat), hipMemcpyDeviceToHost, st));
+    SRT_PASS_TRY(le);
 out:
-    if (ws) (void)hipFreeAsync(ws, st);
-    if (dstat) (void)hipFreeAsync(dstat, st);
-    if (hipStreamSynchronize(st) != hipSuccess && !rc) {
-        srt_set_error("split load: the kernel failed (%s)", hipGetErrorString(hipGetLastError()));
-        rc = SRT_E_DEVICE;
-    }
+    rc = sc.finish(rc, hstat);
     if (!rc) rc = span.end(st, &ms);
     if (!rc && stats) {
         const int32_t sweeps = (int32_t)(uint32_t)hstat[1];

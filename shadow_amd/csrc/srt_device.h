@@ -26,7 +26,7 @@ static __device__ __forceinline__ void srt_max_once(int32_t* p, int v) {
         }                                                                                  \
     } while (0)
 
-/* a HIP-event pair around a span of a stream (the route and envelope passes' own times) */
+/* a HIP-event pair around a span of a stream (the row passes' own times) */
 struct srt_event_span {
     hipEvent_t e[2] = {nullptr, nullptr};
     ~srt_event_span() {
@@ -40,8 +40,17 @@ struct srt_event_span {
         return SRT_OK;
     }
     int end(hipStream_t st, double* ms) {
-        float a = 0;
+        const int rc = stop(st);
+        return rc ? rc : read(ms);
+    }
+    /* end in two halves, for a span that closes before more work joins the stream: stop marks
+     * the span's end, read (any time later) waits for it and adds the span to *ms */
+    int stop(hipStream_t st) {
         SRT_HIPCHK(hipEventRecord(e[1], st));
+        return SRT_OK;
+    }
+    int read(double* ms) {
+        float a = 0;
         SRT_HIPCHK(hipEventSynchronize(e[1]));
         SRT_HIPCHK(hipEventElapsedTime(&a, e[0], e[1]));
         *ms += a;
@@ -332,8 +341,9 @@ void srt_routes_ess_free(int32_t* irp, int32_t* icol, uint32_t* iw, hipStream_t 
 /* linkload.hip: the load pass over nrows rows of pred / hops (stride ldp) and u64 demand (stride
  * ldd) against an in-arc CSR: ADDS into load (one word per CSR position), through (n) and totals
  * (routed, unrouted, self); sorted != 0 promises in-lists with ascending tails (a sparse graph's,
- * an undirected dense graph's: binary search; else the lists are scanned); raises *max_hops, ors the flow forms into *forms, adds the HIP-event
- * time of the kernel to *ms. Returns after the stream. */
+ * an undirected dense graph's: binary search; else the lists are scanned); raises *max_hops, ors
+ * the flow forms into *forms, adds the HIP-event time of the kernel to *ms. Returns after the
+ * stream. */
 int srt_link_load_rows(int n, int nrows, const int32_t* srcs, int src_begin, const int32_t* pred,
                        const int32_t* hops, size_t ldp, const uint64_t* dem, size_t ldd,
                        const int32_t* irp, const int32_t* icol, uint64_t* load, uint64_t* through,

@@ -153,6 +153,18 @@ def test_build_link_load_direct_mode():
                         use_shortest_path=False)
 
 
+def test_build_link_load_empty_demand():
+    """A COO demand with no entry has no source: nothing is routed, and no device is asked for."""
+    g = route_graphs.c1()
+    coo = (np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.uint64))
+    tail, head, load, through, st = build_link_load(g.n, False, g.src, g.dst, g.lat_ns, g.loss,
+                                                    demand=coo, use_shortest_path=True)
+    assert len(tail) == len(head) == len(load) == 0
+    assert (tail.dtype, head.dtype, load.dtype) == (np.int32, np.int32, np.uint64)
+    assert through.dtype == np.uint64 and len(through) == g.n and not through.any()
+    assert (st.routed, st.unrouted, st.self_demand) == (0, 0, 0)
+
+
 def test_topology_link_load_direct_mode():
     """No packet has been counted (a lookup needs the tables, and those a device): the answer is
     empty, costs one build call and leaves the lookup side alone."""

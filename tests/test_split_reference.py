@@ -1,6 +1,7 @@
 """tests/split_reference.py itself (CPU: the oracle's distances, numpy and plain Python): its two
 formulations held to each other, to the canonical link load where nothing is tied, and to hand
-values. The GPU tests (test_gpu_split_load.py) hold splitload.hip to `by_distance`."""
+values. The GPU tests (test_gpu_split_load.py) hold splitload.hip to `by_distance`. Direct mode
+(use_shortest_path = 0) and an empty demand need no device and run through the library here."""
 import numpy as np
 import pytest
 
@@ -9,6 +10,7 @@ import route_graphs
 import split_graphs as sg
 import split_reference as sr
 from route_reference import InArcs
+from shadow_amd.topology import build_split_load
 
 
 def both(g, demand=None):
@@ -94,3 +96,60 @@ def test_hand12_members_are_not_all_tight_arcs():
     assert arcs.u[k] == 2 and one.load[k] == 0.0
     assert one.load[arcs.ptr[3] + 0] == 1.0 and arcs.u[arcs.ptr[3]] == 1
     assert one.unrouted == 8 and one.routed == 3 and one.self_demand == 1
+
+
+def test_build_split_load_direct_mode():
+    """load(s -> t) = (double)c(s, t), through = 0, computed on the host."""
+    g = route_graphs.c1()
+    srcs = np.array([0, 7, 49], np.int32)
+    tail, head, load, through, st = build_split_load(g.n, False, g.src, g.dst, g.lat_ns, g.loss,
+                                                     sources=srcs, use_shortest_path=False)
+    want = [(int(s), t) for s in srcs for t in range(g.n) if t != s]
+    assert list(zip(tail.tolist(), head.tolist())) == want
+    assert (load == 1.0).all() and load.dtype == np.float64
+    assert not through.any() and len(through) == g.n and through.dtype == np.float64
+    assert (st.routed, st.unrouted, st.self_demand) == (3 * 49, 0, 3)
+    assert st.ms_split == 0.0 and st.forms == 0 and st.tied_pairs == 0
+    dem = np.zeros((3, g.n), np.int64)
+    dem[0, 5], dem[1, 7], dem[2, 0], dem[2, 48] = 11, 6, 1 << 40, 3
+    tail, head, load, through, st = build_split_load(g.n, False, g.src, g.dst, g.lat_ns, g.loss,
+                                                     sources=srcs, demand=dem,
+                                                     use_shortest_path=False)
+    assert list(zip(tail.tolist(), head.tolist(), load.tolist())) == [
+        (0, 5, 11.0), (49, 0, float(1 << 40)), (49, 48, 3.0)]
+    assert load.dtype == np.float64 and through.dtype == np.float64
+    assert (st.routed, st.self_demand) == ((1 << 40) + 14, 6) and not through.any()
+    # duplicates add; the total must stay below 2^53, where every sum is exact in f64
+    coo = (np.array([3, 3], np.int32), np.array([9, 9], np.int32), np.array([5, 6], np.uint64))
+    tail, head, load, through, _ = build_split_load(g.n, False, g.src, g.dst, g.lat_ns, g.loss,
+                                                    demand=coo, use_shortest_path=False)
+    assert (tail.tolist(), head.tolist(), load.tolist()) == ([3], [9], [11.0])
+    assert load.dtype == np.float64 and not through.any()
+    most = (np.array([3, 4], np.int32), np.array([9, 9], np.int32),
+            np.array([(1 << 53) - 2, 1], np.uint64))
+    _, _, load, _, st = build_split_load(g.n, False, g.src, g.dst, g.lat_ns, g.loss, demand=most,
+                                         use_shortest_path=False)
+    assert load.tolist() == [float((1 << 53) - 2), 1.0] and st.routed == (1 << 53) - 1
+    big = (most[0], most[1], np.array([(1 << 53) - 1, 1], np.uint64))
+    with pytest.raises(RuntimeError, match="SRT_E_RANGE"):
+        build_split_load(g.n, False, g.src, g.dst, g.lat_ns, g.loss, demand=big,
+                         use_shortest_path=False)
+    ring = route_graphs.ring3000()  # the 2^53 refusal comes first, the completeness check after it
+    with pytest.raises(RuntimeError, match="SRT_E_RANGE"):
+        build_split_load(ring.n, False, ring.src, ring.dst, ring.lat_ns, ring.loss, demand=big,
+                         use_shortest_path=False)
+    with pytest.raises(RuntimeError, match="complete graph"):
+        build_split_load(ring.n, False, ring.src, ring.dst, ring.lat_ns, ring.loss,
+                         use_shortest_path=False)
+
+
+def test_build_split_load_empty_demand():
+    """A COO demand with no entry has no source: nothing is routed, and no device is asked for."""
+    g = route_graphs.c1()
+    coo = (np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.uint64))
+    tail, head, load, through, st = build_split_load(g.n, False, g.src, g.dst, g.lat_ns, g.loss,
+                                                     demand=coo, use_shortest_path=True)
+    assert len(tail) == len(head) == len(load) == 0
+    assert (tail.dtype, head.dtype, load.dtype) == (np.int32, np.int32, np.float64)
+    assert through.dtype == np.float64 and len(through) == g.n and not through.any()
+    assert (st.routed, st.unrouted, st.self_demand) == (0, 0, 0)
